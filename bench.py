@@ -10,9 +10,15 @@ uniform positions, analytic RGB targets. Multi-GPU is data parallel (SURVEY.md Â
   --scaling weak: every rank trains on its own 2^18 batch; `value` = 2^18-sample steps completed by
       all ranks per second.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
       --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the result line. --full adds what takes
+runs of its own: the profiled pass behind `phase_ms` / `roofline` and the CPU baseline
+(`cpu_baseline`); --no-profile / --no-cpu-baseline drop either again. --dump-outputs DIR writes what
+the last timed step left with the caller (DIR/<name>.npy, see dump_outputs); the inputs are seeded,
+so two builds run with the same arguments can be compared array for array.
 """
 import argparse
 import json
@@ -189,6 +195,28 @@ def pmc_traffic(kernel, tag):
     return None
 
 
+DUMP_MAX_ELEMS = 4 << 20  # per array: 16 MiB of float32, three arrays at the most -> under 64 MB in all
+
+
+def dump_outputs(out_dir, arrays):
+    """Write what the last timed step left with the caller as out_dir/<name>.npy (float32; the loss
+    float64): `params` = the fp16 parameters the step updated, `params_fp32` = their fp32 masters
+    (single GPU: with a sharded optimizer a rank holds only its shard), `loss` = the step's loss. An
+    array above DUMP_MAX_ELEMS is cut to a fixed sample (sorted indices of a generator seeded with
+    1337, a function of the array's length alone)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    shapes = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(1337).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -198,8 +226,12 @@ def main():
     ap.add_argument("--config", default=os.path.join(REPO, "tests", "golden", "config_hash.json"))
     ap.add_argument("--log2-hashmap-size", type=int, default=None, help="override encoding.log2_hashmap_size")
     ap.add_argument("--per-level-scale", type=float, default=None, help="override encoding.per_level_scale")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the profiled pass (phase_ms, roofline) and the CPU baseline (cpu_baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (parameters, loss) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: skip the profiled pass")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL on ROCm) or gloo (rehearsal)")
     ap.add_argument("--scaling", choices=["strong", "weak"], default="strong",
                     help="strong: shard the global batch over ranks (configs[4]); weak: a full batch per rank")
@@ -308,8 +340,16 @@ def main():
         dist.all_reduce(e, op=dist.ReduceOp.MAX)
         elapsed = float(e.item())
 
+    dumped = None
+    if args.dump_outputs is not None and rank == 0:
+        # device copies now: the profiled pass of --full trains on
+        dumped = {"params": trainer.params().float()}
+        if world == 1:
+            dumped["params_fp32"] = trainer.params_fp32().clone()
+        dumped_loss = trainer.loss()
+
     phase_ms = None
-    if not args.no_profile:
+    if args.full and not args.no_profile:
         # the profiled pass: the same step on the same batches, events on every PHASE_EVERY-th step
         L.check(L.lib().tcnn_trainer_profile_begin_sampled(trainer.h, PHASE_EVERY))
         for i in range(PHASE_STEPS):
@@ -392,7 +432,12 @@ def main():
                                              f"{nb} binned parameters)", "bound": "hbm", "achieved": achieved,
                                    "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": achieved / PEAK_HBM_GBS,
                                    "traffic": sum(parts) if all(p is not None for p in parts) else None}
-    if world == 1 and not args.no_cpu_baseline:
+    if dumped is not None:
+        import numpy as np
+        arrays = {k: v.cpu().numpy() for k, v in dumped.items()}
+        arrays["loss"] = np.array([dumped_loss], dtype=np.float64)
+        res["dumped_outputs"] = dump_outputs(args.dump_outputs, arrays)
+    if args.full and world == 1 and not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline(cfg)
     print(json.dumps(res))
     if world > 1:

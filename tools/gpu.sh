@@ -3,7 +3,7 @@
 # Steps (each under its own time limit; the job stops at the first failing step):
 #   tests[:<pytest args>]  GPU parity suite (default: all of tests -m gpu)
 #   smoke                  __graft_entry__.smoke()
-#   bench[:<bench args>]   bench.py (default args: none -> the driver's default run incl. CPU baseline)
+#   bench[:<bench args>]   bench.py --full (phase times, roofline and the CPU baseline with the headline figure)
 #   prof[:<bench args>]    rocprofv3 --kernel-trace --stats of bench.py (-> $OUT/prof, top kernels)
 #   pmc[:<groups file>]    PMC passes over a short bench (tools/gpu_pmc.sh) + HBM traffic summary;
 #                          BENCH_EXTRA / PMC_FILTER pass through
@@ -35,11 +35,11 @@ for step in "$@"; do
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$log" 2>&1 || { echo SMOKE_FAILED; tail -20 "$log"; exit 1; }
       tail -1 "$log" ;;
     bench)
-      timeout -k 10 600 python -u bench.py $arg > "$log" 2>&1 || { echo BENCH_FAILED; tail -20 "$log"; exit 1; }
+      timeout -k 10 600 python -u bench.py --full $arg > "$log" 2>&1 || { echo BENCH_FAILED; tail -20 "$log"; exit 1; }
       grep '^{' "$log" | cut -c1-600 ;;
     prof)
       rm -rf "$D/prof$n"
-      timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$D/prof$n" -o run -- python3 bench.py --no-cpu-baseline $arg > "$log" 2>&1 \
+      timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$D/prof$n" -o run -- python3 bench.py --full --no-cpu-baseline $arg > "$log" 2>&1 \
         || { echo PROF_FAILED; tail -20 "$log"; exit 1; }
       python3 tools/prof_top.py "$D/prof$n" | head -12 ;;
     pmc)

@@ -12,7 +12,7 @@ if [ -n "$TESTS" ]; then
 fi
 for v in new base new base; do
   if [ $v = base ]; then export TCNN_LIB_PATH=$AB; else unset TCNN_LIB_PATH; fi
-  timeout -k 10 200 python3 bench.py --no-cpu-baseline > $D/bench_$v.log 2>&1 || { tail -5 $D/bench_$v.log; exit 1; }
+  timeout -k 10 200 python3 bench.py --full --no-cpu-baseline > $D/bench_$v.log 2>&1 || { tail -5 $D/bench_$v.log; exit 1; }
   timeout -k 10 200 python3 tools/dp_floor.py --schedules plain --steps 400 --batch-log2 15 --out $D/floor_$v.json > $D/floor_$v.log 2>&1 || { tail -5 $D/floor_$v.log; exit 1; }
   python3 -c "
 import json

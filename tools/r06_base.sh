@@ -2,7 +2,7 @@
 # rank), and the peer step of 8 ranks time-sharing one GPU (each rank under its own rocprofv3, started by
 # this shell -- no process that touched the GPU launches another)
 cd "${GRAFT_REPO_ROOT:-.}"; export TMPDIR=/tmp; D=gpurun_out/${OUT:-r06_base}; mkdir -p $D
-timeout -k 10 300 python3 bench.py --no-cpu-baseline > $D/bench.log 2>&1 || { tail -5 $D/bench.log; exit 1; }
+timeout -k 10 300 python3 bench.py --full --no-cpu-baseline > $D/bench.log 2>&1 || { tail -5 $D/bench.log; exit 1; }
 grep '^{' $D/bench.log | cut -c1-200
 for s in plain peer; do
   timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $D/prof_$s -o run -- python3 tools/dp_floor.py --schedules $s --steps 400 --batch-log2 ${LOG2B:-15} --out $D/floor_$s.json > $D/prof_$s.log 2>&1 || { tail -5 $D/prof_$s.log; exit 1; }

@@ -9,7 +9,7 @@ for v in new new2 v1 v2 v3 base; do
 done
 for v in new v2 v3 base; do
   case $v in new) unset TCNN_LIB_PATH;; base) export TCNN_LIB_PATH=$P/lib_ab/libtcnn_mi355x.so;; *) export TCNN_LIB_PATH=$P/lib_$v/libtcnn_mi355x.so;; esac
-  timeout -k 10 200 python3 bench.py --no-cpu-baseline > $D/bench_$v.log 2>&1 || { tail -5 $D/bench_$v.log; exit 1; }
+  timeout -k 10 200 python3 bench.py --full --no-cpu-baseline > $D/bench_$v.log 2>&1 || { tail -5 $D/bench_$v.log; exit 1; }
   python3 -c "
 import json
 b=[json.loads(l) for l in open('$D/bench_$v.log') if l.startswith('{')][0]

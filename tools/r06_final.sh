@@ -7,7 +7,7 @@ if [ -z "$SKIP_TESTS" ]; then
   timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $D/smoke.log 2>&1 || { tail -10 $D/smoke.log; exit 1; }
   tail -2 $D/smoke.log
 fi
-timeout -k 10 300 python3 bench.py > $D/bench.log 2>&1 || { tail -5 $D/bench.log; exit 1; }
+timeout -k 10 300 python3 bench.py --full > $D/bench.log 2>&1 || { tail -5 $D/bench.log; exit 1; }
 grep '^{' $D/bench.log | cut -c1-240
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $D/prof -o run -- python3 bench.py --no-cpu-baseline --no-profile --steps 200 > $D/prof.log 2>&1 || { tail -5 $D/prof.log; exit 1; }
 f=$(find $D/prof -name '*kernel_stats.csv' | head -1); cp "$f" $D/kernel_stats.csv

@@ -12,7 +12,7 @@ for lb in ${LOG2B:-15}; do
   python3 -c "import json; d=json.load(open('$D/floor_$lb.json')); [print($lb, r['schedule'][:40], round(r['gpu_us_per_step'],2), round(r['host_issue_us_per_step'],2)) for r in d['rows']]"
 done
 if [ -n "$BENCH" ]; then
-  timeout -k 10 300 python3 bench.py --no-cpu-baseline > $D/bench.log 2>&1 || { tail -5 $D/bench.log; exit 1; }
+  timeout -k 10 300 python3 bench.py --full --no-cpu-baseline > $D/bench.log 2>&1 || { tail -5 $D/bench.log; exit 1; }
   grep '^{' $D/bench.log | cut -c1-200
 fi
 if [ -n "$PROF" ]; then

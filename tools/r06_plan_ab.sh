@@ -4,7 +4,7 @@ cd "${GRAFT_REPO_ROOT:-.}"; export TMPDIR=/tmp; D=gpurun_out/${OUT:-r06_plan}; m
 for plan in range feature default; do
   if [ $plan = default ]; then unset TCNN_GRID_BWD_PLAN; else export TCNN_GRID_BWD_PLAN=$plan; fi
   timeout -k 10 200 python3 tools/dp_floor.py --schedules plain --steps 400 --batch-log2 15 --out $D/floor_$plan.json > $D/floor_$plan.log 2>&1 || { tail -5 $D/floor_$plan.log; exit 1; }
-  timeout -k 10 200 python3 bench.py --no-cpu-baseline > $D/bench_$plan.log 2>&1 || { tail -5 $D/bench_$plan.log; exit 1; }
+  timeout -k 10 200 python3 bench.py --full --no-cpu-baseline > $D/bench_$plan.log 2>&1 || { tail -5 $D/bench_$plan.log; exit 1; }
   timeout -k 10 200 python3 tools/c3_time.py > $D/c3_$plan.json 2> $D/c3_$plan.err || { tail -5 $D/c3_$plan.err; exit 1; }
   python3 -c "
 import json

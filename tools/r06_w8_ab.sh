@@ -3,7 +3,7 @@
 cd "${GRAFT_REPO_ROOT:-.}"; export TMPDIR=/tmp; D=gpurun_out/${OUT:-r06_w8}; mkdir -p $D
 for v in 4 8 4 8; do
   if [ $v = 8 ]; then export TCNN_LIB_PATH=$PWD/neuralbtf-tiny-cuda-nn_amd/lib_ab/libtcnn_mi355x.so; else unset TCNN_LIB_PATH; fi
-  timeout -k 10 200 python3 bench.py --no-cpu-baseline > $D/bench_$v.log 2>&1 || { tail -5 $D/bench_$v.log; exit 1; }
+  timeout -k 10 200 python3 bench.py --full --no-cpu-baseline > $D/bench_$v.log 2>&1 || { tail -5 $D/bench_$v.log; exit 1; }
   timeout -k 10 200 python3 tools/dp_floor.py --schedules plain --steps 400 --batch-log2 15 --out $D/floor_$v.json > $D/floor_$v.log 2>&1 || { tail -5 $D/floor_$v.log; exit 1; }
   python3 -c "
 import json
