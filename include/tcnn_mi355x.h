@@ -69,6 +69,9 @@ tcnn_module* tcnn_create_network_with_input_encoding(uint32_t n_input_dims, uint
 tcnn_module* tcnn_create_network(uint32_t n_input_dims, uint32_t n_output_dims, const char* network_json);
 /* cpp::create_encoding(n_input_dims, encoding, requested_precision) */
 tcnn_module* tcnn_create_encoding(uint32_t n_input_dims, const char* encoding_json, int precision);
+/* create_encoding<T>(n_dims_to_encode, encoding, alignment): the encoded width padded to a multiple of
+   `alignment` (0: no padding). Not for a grid encoding standing alone. */
+tcnn_module* tcnn_create_encoding_aligned(uint32_t n_input_dims, const char* encoding_json, int precision, uint32_t alignment);
 void tcnn_module_destroy(tcnn_module* m);
 
 /* Module::inference(stream, n, input, output, params) (cpp_api.h:91) */

@@ -210,11 +210,16 @@ struct ModuleNWIE : ModuleBase {
 	std::string name() const override { return "NetworkWithInputEncoding"; }
 };
 
-// Parameter-free encodings (OneBlob, Identity) as a module (cpp_api.cu:145-149). Encoding modules take
-// any batch size (per-point kernels with bounds checks, like the reference); networks keep the 256 rule.
+// OneBlob, Identity and composite encodings (Composite, SphericalHarmonics, TriangleWave) as a module
+// (cpp_api.cu:145-149); a composite's nested grids make it own parameters and a gradient buffer.
+// Encoding modules take any batch size (per-point kernels with bounds checks, like the reference);
+// networks keep the 256 rule.
 struct ModuleEncoding : ModuleBase {
 	EncodingHost enc;
-	ModuleEncoding(uint32_t n_in, const json& j) : enc(n_in, j) {}
+	DevBuf grad32;
+	ModuleEncoding(uint32_t n_in, const json& j, uint32_t alignment) : enc(n_in, j) {
+		if (alignment > 0) enc.set_alignment(alignment);
+	}
 	void inference(hipStream_t st, uint32_t n, const float* in, void* out, const void* params) override {
 		enc.forward_aos(st, n, in, params, out);
 	}
@@ -222,16 +227,31 @@ struct ModuleEncoding : ModuleBase {
 		inference(st, n, in, out, params);
 		return nullptr;
 	}
-	void backward(hipStream_t st, const ModuleCtx*, uint32_t n, float* dL_din, const void* dL_dout, void*, const float* in, const void*,
-	              const void*) override {
-		if (dL_din) enc.backward_input(st, n, in, dL_dout, dL_din);
+	void backward(hipStream_t st, const ModuleCtx*, uint32_t n, float* dL_din, const void* dL_dout, void* dL_dparams, const float* in,
+	              const void*, const void* params) override {
+		if (dL_din) enc.backward_input(st, n, in, dL_dout, dL_din, params);
+		if (!dL_dparams || !enc.n_params()) return;
+		grad32.reserve((size_t)enc.n_params() * 4);
+		enc.backward_params(st, n, in, dL_dout, grad32.as<float>());
+		launch_cast_f32_f16(st, grad32.as<float>(), dL_dparams, enc.n_params());
+	}
+	// (backward_backward_input: ModuleBase's "not implemented", for composites with grids too)
+	GridEncodingHost* grid_encoding() override {  // max_level of nested grids: not through the composite yet
+		if (enc.kind == EncKind::Composite) throw std::runtime_error(enc.name() + ": max_level is not implemented by the MI355X engine yet");
+		return nullptr;
 	}
 	uint32_t n_input_dims() const override { return enc.n_dims; }
 	uint32_t n_output_dims() const override { return enc.padded_output_width(); }
-	uint64_t n_params() const override { return 0; }
-	void initialize_params(uint64_t, float*, float) override {}
+	uint64_t n_params() const override { return enc.n_params(); }
+	void initialize_params(uint64_t seed, float* p, float scale) override {
+		if (!enc.n_params()) return;
+		Pcg32 rng{seed};
+		std::vector<float> host(enc.n_params());
+		enc.initialize_params(rng, host.data(), scale);
+		TCNN_HIP_CHECK(hipMemcpy(p, host.data(), host.size() * 4, hipMemcpyHostToDevice));
+	}
 	json hyperparams() const override { return enc.hyperparams(); }
-	std::string name() const override { return enc.kind == EncKind::OneBlob ? "OneBlobEncoding" : "IdentityEncoding"; }
+	std::string name() const override { return enc.name(); }
 };
 
 struct ModuleGrid : ModuleBase {
@@ -374,17 +394,27 @@ tcnn_module* tcnn_create_network(uint32_t n_in, uint32_t n_out, const char* net)
 	});
 }
 
-tcnn_module* tcnn_create_encoding(uint32_t n_in, const char* enc, int precision) {
+// create_encoding<T>(n_dims, encoding, alignment) (encoding.cu:131-145); alignment 0: none. A grid
+// standing alone keeps its own module and takes no alignment here.
+tcnn_module* tcnn_create_encoding_aligned(uint32_t n_in, const char* enc, int precision, uint32_t alignment) {
 	return guard_ptr<tcnn_module>([&] {
 		TCNN_CHECK(precision == TCNN_PRECISION_FP16, "create_encoding: only Fp16 precision is implemented by the MI355X engine");
 		json j = parse_json(enc);
 		const std::string ot = j.is_object() && j.find("otype") != j.end() ? j["otype"].get<std::string>() : "OneBlob";
 		TCNN_CHECK(EncodingHost::known(ot), "Encoding '" + ot + "' is not implemented by the MI355X engine yet");
-		auto* r = new tcnn_module;
-		if (ieq(ot, "OneBlob") || ieq(ot, "Identity")) r->m = std::make_unique<ModuleEncoding>(n_in, j);
-		else r->m = std::make_unique<ModuleGrid>(n_in, j);
-		return r;
+		auto r = std::make_unique<tcnn_module>();
+		const bool is_grid = ieq(ot, "HashGrid") || ieq(ot, "Grid") || ieq(ot, "TiledGrid") || ieq(ot, "DenseGrid");
+		if (!is_grid) r->m = std::make_unique<ModuleEncoding>(n_in, j, alignment);
+		else {
+			TCNN_CHECK(alignment == 0, "create_encoding: a grid encoding module takes no alignment");
+			r->m = std::make_unique<ModuleGrid>(n_in, j);
+		}
+		return r.release();
 	});
+}
+
+tcnn_module* tcnn_create_encoding(uint32_t n_in, const char* enc, int precision) {
+	return tcnn_create_encoding_aligned(n_in, enc, precision, 0);
 }
 
 void tcnn_module_destroy(tcnn_module* m) { delete m; }

@@ -1,52 +1,13 @@
 // encodings.hip -- OneBlob and Identity encodings for gfx950 (reference encodings/oneblob.h,
 // encodings/identity.h). Output AoS fp16 [B][out_stride] (their preferred layout), padding
 // columns set to 1 (oneblob.h:200-203, identity.h:62-63).
+#include "encodings_device.h"
 #include "kernels.h"
 
 namespace tcnn_amd {
 
-// quartic_cdf / quartic (common_device.h:905-920). The reference is compiled by nvcc with FMA
-// contraction on; its contraction points are written out as explicit FMAs here (this file is
-// compiled with -ffp-contract=off), the same ones the oracle uses.
-__device__ __forceinline__ float quartic_cdf(float x, float inv_radius) {
-	const float u = x * inv_radius;
-	const float u2 = u * u;
-	const float u4 = u2 * u2;
-	float p = __builtin_fmaf(-(2.0f / 3.0f), u2, 1.0f);
-	p = __builtin_fmaf(1.0f / 5.0f, u4, p);
-	return fmaxf(0.0f, fminf(1.0f, __builtin_fmaf((15.0f / 16.0f) * u, p, 0.5f)));
-}
-
-__device__ __forceinline__ float quartic_cdf_deriv(float x, float inv_radius) {
-	const float u = x * inv_radius;
-	const float tmp = fmaxf(__builtin_fmaf(-u, u, 1.0f), 0.0f);
-	return (15.0f / 16.0f) * tmp * tmp * inv_radius;
-}
-
-// Wrapped CDF at a bin's left boundary (one_blob_subwarp_aligned, oneblob.h:48-51). The two wrap
-// terms are clamped for all but the bins within one bin width of the domain's ends: quartic_cdf is
-// exactly 0 for u <= -T and exactly 1 for u >= T with T = 1.0625 (every fp32 u checked with this op
-// sequence by tools/quartic_clamp_check.c; the last unclamped values are at |u| ~ 1.004), so those
-// terms are skipped when no lane of the wave needs them, with bit-identical sums (same addition order).
-// The forward is VALU-bound (27 polynomial evaluations per 8 bins before); this removes ~2/3 of them.
-__device__ __forceinline__ float wrapped_cdf(float boundary, float x, float n_bins) {
-	constexpr float T = 1.0625f;
-	const float d = boundary - x;
-	const float c = quartic_cdf(d, n_bins);
-	// the ballot makes the test wave-uniform (a scalar branch, not predication); inside it every lane
-	// evaluates the term, which is exact either way
-	float lo = 0.0f, hi = 1.0f;
-	if (__builtin_amdgcn_ballot_w64(!((d - 1.0f) * n_bins <= -T))) lo = quartic_cdf(d - 1.0f, n_bins);
-	if (__builtin_amdgcn_ballot_w64(!((d + 1.0f) * n_bins >= T))) hi = quartic_cdf(d + 1.0f, n_bins);
-	return c + lo + hi;
-}
-
 // OneBlob forward, one thread per (sample, dim): all n_bins outputs of that dimension.
-// The reference evaluates each bin's left CDF in its own lane and takes the right CDF from lane
-// (bin + 1) with __shfl_sync(..., bin + 1, n_bins) (oneblob.h:53-62). On its 32-lane warps a shuffle
-// width above 32 acts as width 32, so for n_bins > 32 the source lane wraps inside each 32-bin
-// group: bin b reads the left CDF of bin (b & ~31) + ((b + 1) & 31), and only the last bin of the
-// dimension adds the wrap-around 1. This kernel reproduces exactly that (S = min(n_bins, 32)).
+// (oneblob_fwd_dim, encodings_device.h, reproduces the reference's shuffle semantics).
 __global__ __launch_bounds__(256) void k_oneblob_fwd(uint32_t B, uint32_t D, uint32_t n_bins, uint32_t log2_bins,
                                                       const float* __restrict__ x, uint32_t x_stride, _Float16* __restrict__ out,
                                                       uint32_t out_stride, uint32_t n_pad) {
@@ -59,21 +20,8 @@ __global__ __launch_bounds__(256) void k_oneblob_fwd(uint32_t B, uint32_t D, uin
 		return;
 	}
 	const float xv = x[(size_t)i * x_stride + d];
-	const float nb = (float)n_bins;
-	const uint32_t S = n_bins < 32 ? n_bins : 32;
 	_Float16* o = row + d * n_bins;
-	for (uint32_t g = 0; g < n_bins; g += S) {
-		const float first = wrapped_cdf(scalbnf((float)g, -(int)log2_bins), xv, nb);
-		float left = first;
-		for (uint32_t j = 0; j < S; ++j) {
-			const uint32_t b = g + j;
-			float right;
-			if (j + 1 < S) right = wrapped_cdf(scalbnf((float)(b + 1), -(int)log2_bins), xv, nb);
-			else right = first + (b == n_bins - 1 ? 1.0f : 0.0f);
-			o[b] = f16_rn(right - left);
-			left = right;
-		}
-	}
+	oneblob_fwd_dim(xv, n_bins, log2_bins, [&](uint32_t b, _Float16 v) { o[b] = v; });
 }
 
 // Same values, 8 bins per thread and one 16-byte store (n_bins >= 8): consecutive threads write
@@ -131,17 +79,7 @@ __global__ __launch_bounds__(256) void k_oneblob_bwd(uint32_t B, uint32_t D, uin
 	if (t >= B * D) return;
 	const uint32_t i = t / D, d = t % D;
 	const float xv = x[(size_t)i * x_stride + d];
-	const float nb = (float)n_bins;
-	float left = quartic_cdf_deriv(-xv, nb) + quartic_cdf_deriv(-xv - 1.0f, nb) + quartic_cdf_deriv(-xv + 1.0f, nb);
-	float result = 0.0f;
-	for (uint32_t k = 0; k < n_bins; ++k) {
-		const float rb = scalbnf((float)(k + 1), -(int)log2_bins);
-		const float right = quartic_cdf_deriv(rb - xv, nb) + quartic_cdf_deriv(rb - xv - 1.0f, nb) + quartic_cdf_deriv(rb - xv + 1.0f, nb);
-		const float deriv = left - right;
-		left = right;
-		result = __builtin_fmaf((float)dy[(size_t)i * dy_stride + d * n_bins + k], deriv, result);
-	}
-	dx[(size_t)i * dx_stride + d] = result;
+	dx[(size_t)i * dx_stride + d] = oneblob_bwd_dim(xv, n_bins, log2_bins, dy + (size_t)i * dy_stride + d * n_bins);
 }
 
 static uint32_t ilog2(uint32_t v) {
@@ -185,7 +123,7 @@ __global__ __launch_bounds__(256) void k_identity_fwd(uint32_t B, uint32_t D, fl
 	const uint32_t fan = D + n_pad;
 	if (t >= B * fan) return;
 	const uint32_t i = t / fan, j = t % fan;
-	out[(size_t)i * out_stride + j] = j < D ? f16_rn(__builtin_fmaf(x[(size_t)i * x_stride + j], scale, offset)) : (_Float16)1.0f;
+	out[(size_t)i * out_stride + j] = j < D ? identity_fwd_value(x[(size_t)i * x_stride + j], scale, offset) : (_Float16)1.0f;
 }
 
 // identity_backward (identity.h:68-85): dL/dx = (T)(dL/dy * scale) -- stored as fp32 here.
@@ -194,7 +132,7 @@ __global__ __launch_bounds__(256) void k_identity_bwd(uint32_t B, uint32_t D, fl
 	const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
 	if (t >= B * D) return;
 	const uint32_t i = t / D, j = t % D;
-	dx[(size_t)i * dx_stride + j] = (float)f16_rn((float)dy[(size_t)i * dy_stride + j] * scale);
+	dx[(size_t)i * dx_stride + j] = identity_bwd_value(dy[(size_t)i * dy_stride + j], scale);
 }
 
 void launch_identity_fwd(hipStream_t st, uint32_t B, uint32_t D, float scale, float offset, const float* x, uint32_t x_stride,

@@ -104,7 +104,7 @@ template <uint32_t D, HashType H>
 __global__ __launch_bounds__(256) void k_grid_fwd_aos_f2(uint32_t B, const float* __restrict__ pos, uint32_t pstride,
                                                          const uint32_t* __restrict__ table, _Float16* __restrict__ out,
                                                          uint32_t out_stride, const LevelInfo* __restrict__ levels, uint32_t hash_grid,
-                                                         uint32_t interp_u, const GridOpts o, uint32_t L) {
+                                                         uint32_t interp_u, const GridOpts o, uint32_t L, uint32_t row_cols) {
 	__shared__ uint32_t tile[64 * 65];  // [point][level], row stride 65 (conflict-free column writes)
 	const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 	const uint32_t i = blockIdx.x * 64 + lane;
@@ -155,12 +155,14 @@ __global__ __launch_bounds__(256) void k_grid_fwd_aos_f2(uint32_t B, const float
 		tile[lane * 65 + level] = __builtin_bit_cast(uint32_t, r);
 	}
 	__syncthreads();
-	const uint32_t row2 = out_stride / 2;  // half2 columns per output row (grid features + zero padding)
+	// half2 columns written per output row (grid features + zero padding): the whole row, or the first
+	// row_cols columns of it when the grid is a slice of a wider row (a composite's part)
+	const uint32_t row2 = row_cols / 2, stride2 = out_stride / 2;
 	uint32_t* o32 = (uint32_t*)out;
 	for (uint32_t idx = threadIdx.x; idx < 64 * row2; idx += 256) {
 		const uint32_t p = idx / row2, c2 = idx % row2;
 		const uint32_t ip = blockIdx.x * 64 + p;
-		if (ip < B) o32[(size_t)ip * row2 + c2] = c2 < L ? tile[p * 65 + c2] : 0u;
+		if (ip < B) o32[(size_t)ip * stride2 + c2] = c2 < L ? tile[p * 65 + c2] : 0u;
 	}
 }
 
@@ -248,18 +250,21 @@ static void grid_fwd_f(hipStream_t st, uint32_t F, HashType h, dim3 g, uint32_t 
 
 void launch_grid_fwd(hipStream_t st, uint32_t D, uint32_t F, HashType h, uint32_t B, uint32_t L,
                      const float* pos, uint32_t pos_stride, const void* table16, void* out16, bool soa,
-                     uint32_t out_stride, const LevelInfo* levels, bool hash_grid, Interp interp, const GridOpts& go) {
+                     uint32_t out_stride, const LevelInfo* levels, bool hash_grid, Interp interp, const GridOpts& go,
+                     uint32_t aos_row_cols) {
 	if (B == 0) return;
-	if (!soa && F == 2 && L <= 64 && out_stride % 2 == 0 && interp != Interp::Nearest) {
+	// aos_row_cols (0: the whole row): the columns of an AoS row this launch may write (even, like out_stride)
+	const uint32_t row_cols = aos_row_cols ? aos_row_cols : out_stride;
+	if (!soa && F == 2 && L <= 64 && out_stride % 2 == 0 && row_cols % 2 == 0 && interp != Interp::Nearest) {
 		const dim3 g2(div_round_up(B, 64));
 		const uint32_t* t32 = (const uint32_t*)table16;
 		_Float16* o16 = (_Float16*)out16;
 		const uint32_t hg = hash_grid ? 1u : 0u, in = (uint32_t)interp;
 #define AOS2(DD)                                                                                                                   \
 	switch (h) {                                                                                                                   \
-		case HashType::Prime: hipLaunchKernelGGL((k_grid_fwd_aos_f2<DD, HashType::Prime>), g2, dim3(256), 0, st, B, pos, pos_stride, t32, o16, out_stride, levels, hg, in, go, L); break; \
-		case HashType::ReversedPrime: hipLaunchKernelGGL((k_grid_fwd_aos_f2<DD, HashType::ReversedPrime>), g2, dim3(256), 0, st, B, pos, pos_stride, t32, o16, out_stride, levels, hg, in, go, L); break; \
-		default: hipLaunchKernelGGL((k_grid_fwd_aos_f2<DD, HashType::CoherentPrime>), g2, dim3(256), 0, st, B, pos, pos_stride, t32, o16, out_stride, levels, hg, in, go, L); break; \
+		case HashType::Prime: hipLaunchKernelGGL((k_grid_fwd_aos_f2<DD, HashType::Prime>), g2, dim3(256), 0, st, B, pos, pos_stride, t32, o16, out_stride, levels, hg, in, go, L, row_cols); break; \
+		case HashType::ReversedPrime: hipLaunchKernelGGL((k_grid_fwd_aos_f2<DD, HashType::ReversedPrime>), g2, dim3(256), 0, st, B, pos, pos_stride, t32, o16, out_stride, levels, hg, in, go, L, row_cols); break; \
+		default: hipLaunchKernelGGL((k_grid_fwd_aos_f2<DD, HashType::CoherentPrime>), g2, dim3(256), 0, st, B, pos, pos_stride, t32, o16, out_stride, levels, hg, in, go, L, row_cols); break; \
 	}
 		if (D == 2) { AOS2(2) }
 		else if (D == 3) { AOS2(3) }

@@ -171,7 +171,8 @@ void launch_trim_cast(hipStream_t st, uint32_t B, uint32_t in_stride, uint32_t n
 // AoS [i*out_stride + l*F + f].
 void launch_grid_fwd(hipStream_t st, uint32_t D, uint32_t F, HashType h, uint32_t B, uint32_t L,
                      const float* pos, uint32_t pos_stride, const void* table16, void* out16, bool soa,
-                     uint32_t out_stride, const LevelInfo* levels, bool hash_grid, Interp interp, const GridOpts& opts = GridOpts{});
+                     uint32_t out_stride, const LevelInfo* levels, bool hash_grid, Interp interp, const GridOpts& opts = GridOpts{},
+                     uint32_t aos_row_cols = 0);
 
 // Grid backward: dLdy layout 0 = level-major pairs ([l][i][F] halves), 1 = SoA ([(l*F+f)*B + i]),
 // 2 = AoS ([i*dy_stride + l*F + f]).
@@ -319,6 +320,38 @@ void launch_identity_fwd(hipStream_t st, uint32_t B, uint32_t D, float scale, fl
                          void* out16, uint32_t out_stride, uint32_t n_pad);
 void launch_identity_bwd(hipStream_t st, uint32_t B, uint32_t D, float scale, const void* dy16, uint32_t dy_stride, float* dx,
                          uint32_t dx_stride);
+
+// Composite encodings (composite.hip; reference encodings/composite.h with Concatenation, and
+// spherical_harmonics.h / triangle_wave.h): the parts of one encoded AoS row [B][width]. A part reads
+// input columns [in_col, in_col + n_in) and owns output columns [out_col, out_col + width): n_values
+// encoded values and width - n_values padding columns (SphericalHarmonics: 1, before the values;
+// TriangleWave / OneBlob / Identity: 1, after them; grid: 0, after them). The table travels by value.
+enum : uint32_t { COMP_SH = 0, COMP_TRIANGLE = 1, COMP_ONEBLOB = 2, COMP_IDENTITY = 3, COMP_GRID = 4 };
+constexpr uint32_t COMP_MAX_PARTS = 16, COMP_MAX_INPUTS = 64, COMP_MAX_WIDTH = 256;
+constexpr uint32_t COMP_SLOT_ZERO = 0xFF;
+struct CompPart {
+	uint32_t kind, in_col, n_in, out_col, width, n_values;
+	uint32_t p0;     // SH degree | TriangleWave n_frequencies | OneBlob n_bins
+	uint32_t p1;     // OneBlob log2(n_bins)
+	float f0, f1;    // Identity scale, offset
+};
+struct CompTable {
+	uint32_t n_parts, n_in, width;
+	uint32_t fwd_work;  // any column that k_composite_fwd writes
+	CompPart parts[COMP_MAX_PARTS];
+	uint32_t grid_cols[COMP_MAX_WIDTH / 32];  // bit c: column c holds a nested grid's value (its own launch writes it)
+	// backward work: slot s is (part, input column) -- one per SH part, one per input column of the other
+	// parameter-free parts, and (COMP_SLOT_ZERO, column) for every input column that no part reads
+	uint32_t n_slots;
+	uint8_t slot_part[COMP_MAX_INPUTS], slot_col[COMP_MAX_INPUTS];
+};
+// every column of every row that no nested grid's own forward writes (values of the parameter-free
+// parts and all padding, the grids' included): one launch
+void launch_composite_fwd(hipStream_t st, uint32_t B, const float* x, void* out16, const CompTable& t);
+// dL/dx fp32 [B][n_in] of the parameter-free parts' columns and zeros in the unread columns (plain
+// stores); dy16 AoS fp16 [B][dy_stride]
+void launch_composite_bwd_input(hipStream_t st, uint32_t B, const float* x, const void* dy16, uint32_t dy_stride, float* dx,
+                                const CompTable& t);
 
 void launch_probe_hfma(hipStream_t st, const void* a, const void* b, const void* c, void* out, uint32_t n_pairs);
 // Diagnostic: the config_hash fused (pipelined) kernel with s_memtime phase stamps (prof: [blocks*8][8] u64).

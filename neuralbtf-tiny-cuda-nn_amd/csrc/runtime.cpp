@@ -476,9 +476,16 @@ json AdamHost::hyperparams() const {
 // ------------------------------------------------------------------------------------------
 // Encodings (reference src/encoding.cu:77-150)
 // ------------------------------------------------------------------------------------------
+static bool is_grid_otype(const std::string& eo) {
+	return ieq(eo, "HashGrid") || ieq(eo, "Grid") || ieq(eo, "TiledGrid") || ieq(eo, "DenseGrid");
+}
+static bool is_composite_otype(const std::string& eo) {
+	return ieq(eo, "Composite") || ieq(eo, "NRC") || ieq(eo, "OneBlobFrequency") || ieq(eo, "SphericalHarmonics") ||
+	       ieq(eo, "TriangleWave");
+}
+
 bool EncodingHost::known(const std::string& eo) {
-	return ieq(eo, "HashGrid") || ieq(eo, "Grid") || ieq(eo, "TiledGrid") || ieq(eo, "DenseGrid") || ieq(eo, "OneBlob") ||
-	       ieq(eo, "Identity");
+	return is_grid_otype(eo) || ieq(eo, "OneBlob") || ieq(eo, "Identity") || is_composite_otype(eo);
 }
 
 EncodingHost::EncodingHost(uint32_t n_dims_to_encode, const json& enc) : n_dims(n_dims_to_encode) {
@@ -492,16 +499,179 @@ EncodingHost::EncodingHost(uint32_t n_dims_to_encode, const json& enc) : n_dims(
 		kind = EncKind::Identity;
 		scale = jval<float>(enc, "scale", 1.0f);  // encoding.cu:77-79
 		offset = jval<float>(enc, "offset", 0.0f);
+	} else if (is_composite_otype(eo)) {
+		kind = EncKind::Composite;
+		if (ieq(eo, "Composite")) {
+			composite_otype = "Composite";
+			parse_composite(enc);
+		} else if (ieq(eo, "NRC") || ieq(eo, "OneBlobFrequency")) {  // encoding.cu:93-115
+			composite_otype = "Composite";
+			const json tri = {{"n_dims_to_encode", 3}, {"otype", "TriangleWave"}, {"n_frequencies", jval<uint32_t>(enc, "n_frequencies", 12u)}};
+			const json blob = {{"n_dims_to_encode", 5}, {"otype", "OneBlob"}, {"n_bins", jval<uint32_t>(enc, "n_bins", 4u)}};
+			const json rest = {{"otype", "Identity"}};
+			parse_composite(json{{"otype", "Composite"}, {"nested", json::array({tri, blob, rest})}});
+		} else {  // SphericalHarmonics / TriangleWave standing alone: one part over every input column
+			composite_otype = ieq(eo, "SphericalHarmonics") ? "SphericalHarmonics" : "TriangleWave";
+			add_part(n_dims_to_encode, 0, enc);
+		}
+		TCNN_CHECK(n_dims <= COMP_MAX_INPUTS, "CompositeEncoding: at most " + std::to_string(COMP_MAX_INPUTS) + " input dims");
+		TCNN_CHECK(parts.size() <= COMP_MAX_PARTS, "CompositeEncoding: at most " + std::to_string(COMP_MAX_PARTS) + " nested encodings");
+		// nested encodings that share an input column are refused: the reference's dL/dinput is then
+		// whatever the last of them wrote (order-dependent), and the plain stores here rely on it
+		std::vector<int> owner(n_dims, -1);
+		for (size_t i = 0; i < parts.size(); ++i) {
+			const Part& p = parts[i];
+			TCNN_CHECK(p.in_col + p.n_in <= n_dims, "CompositeEncoding: nested encoding " + std::to_string(i) + " reads input dims [" +
+			                                            std::to_string(p.in_col) + ", " + std::to_string(p.in_col + p.n_in) +
+			                                            ") beyond the composite's " + std::to_string(n_dims));
+			for (uint32_t c = p.in_col; c < p.in_col + p.n_in; ++c) {
+				TCNN_CHECK(owner[c] < 0, "CompositeEncoding: nested encodings " + std::to_string(owner[c]) + " and " + std::to_string(i) +
+				                             " overlap in input dim " + std::to_string(c) + "; overlapping ranges are not supported");
+				owner[c] = (int)i;
+			}
+		}
+		layout(1);
 	} else {
 		kind = EncKind::Grid;
 		grid = std::make_unique<GridEncodingHost>(n_dims_to_encode, enc);
 	}
 }
 
+// CompositeEncoding::CompositeEncoding (composite.h:138-186)
+void EncodingHost::parse_composite(const json& enc) {
+	TCNN_CHECK(jhas(enc, "nested") && enc["nested"].is_array(), "Must provide an array of nested encodings to CompositeEncoding.");
+	const std::string red = jval<std::string>(enc, "reduction", "Concatenation");
+	TCNN_CHECK(ieq(red, "Concatenation") || ieq(red, "Sum") || ieq(red, "Product"), "Invalid reduction type: " + red);
+	TCNN_CHECK(ieq(red, "Concatenation"),
+	           "CompositeEncoding: reduction '" + red + "' is not implemented by the MI355X engine yet (only Concatenation)");
+	const json& nested = enc["nested"];
+	uint32_t total = 0;
+	for (size_t i = 0; i < nested.size(); ++i) {
+		total += jval<uint32_t>(nested[i], "n_dims_to_encode", 0u);
+		if (jhas(nested[i], "dims_to_encode_begin")) {
+			total = 0xFFFFFFFFu;
+			break;
+		}
+	}
+	TCNN_CHECK(total == 0xFFFFFFFFu || total <= n_dims, "CompositeEncoding: nested encodings must not encode more dims " +
+	                                                        std::to_string(total) + " than composite " + std::to_string(n_dims));
+	uint32_t unspecified = total == 0xFFFFFFFFu ? 0xFFFFFFFFu : n_dims - total;
+	uint32_t off = 0;
+	for (size_t i = 0; i < nested.size(); ++i) {
+		uint32_t n;
+		if (jhas(nested[i], "n_dims_to_encode")) {
+			// dims_to_encode_begin counts only beside n_dims_to_encode (composite.h:166-171)
+			if (jhas(nested[i], "dims_to_encode_begin")) off = nested[i]["dims_to_encode_begin"].get<uint32_t>();
+			n = nested[i]["n_dims_to_encode"].get<uint32_t>();
+		} else {
+			TCNN_CHECK(unspecified != 0xFFFFFFFFu, "CompositeEncoding: may only leave 'n_dims_to_encode' unspecified for a single nested encoding");
+			n = unspecified;
+			unspecified = 0xFFFFFFFFu;
+		}
+		if (n > 0) add_part(n, off, nested[i]);
+		off += n;
+	}
+}
+
+void EncodingHost::add_part(uint32_t n_in, uint32_t in_col, const json& enc) {
+	const std::string eo = jval<std::string>(enc, "otype", "OneBlob");
+	TCNN_CHECK(!ieq(eo, "Composite") && !ieq(eo, "NRC") && !ieq(eo, "OneBlobFrequency"),
+	           "CompositeEncoding: a nested Composite encoding is not implemented by the MI355X engine yet");
+	TCNN_CHECK(known(eo), "Encoding '" + eo + "' is not implemented by the MI355X engine yet");
+	Part p;
+	p.n_in = n_in;
+	p.in_col = in_col;
+	if (ieq(eo, "SphericalHarmonics")) {  // spherical_harmonics.h:105-120
+		p.kind = COMP_SH;
+		p.p0 = jval<uint32_t>(enc, "degree", 4u);
+		TCNN_CHECK(n_in == 3, "Can only encode 3D directions in spherical harmonics.");
+		TCNN_CHECK(p.p0 > 0, "Spherical harmonics must have positive degree.");
+		TCNN_CHECK(p.p0 <= 8, "Spherical harmonics are only implemented up to degree 8.");
+		p.n_values = p.p0 * p.p0;
+	} else if (ieq(eo, "TriangleWave")) {
+		p.kind = COMP_TRIANGLE;
+		p.p0 = jval<uint32_t>(enc, "n_frequencies", 12u);
+		p.n_values = n_in * p.p0;
+	} else if (ieq(eo, "OneBlob")) {
+		p.kind = COMP_ONEBLOB;
+		p.p0 = jval<uint32_t>(enc, "n_bins", 16u);
+		TCNN_CHECK(p.p0 > 0 && (p.p0 & (p.p0 - 1)) == 0, "Number of bins must be a power of 2");
+		p.n_values = n_in * p.p0;
+	} else if (ieq(eo, "Identity")) {
+		p.kind = COMP_IDENTITY;
+		p.f0 = jval<float>(enc, "scale", 1.0f);
+		p.f1 = jval<float>(enc, "offset", 0.0f);
+		p.n_values = n_in;
+	} else {
+		p.kind = COMP_GRID;
+		p.grid = std::make_unique<GridEncodingHost>(n_in, enc);
+		p.bufs = std::make_unique<GridBwdBufs>();
+		p.n_values = p.grid->n_features;
+	}
+	parts.push_back(std::move(p));
+}
+
+// composite.h:188-198 (each part's output alignment), then Encoding::set_alignment on the composite
+// (encoding.h:70, composite.h:380-384: the last part takes the rest)
+void EncodingHost::layout(uint32_t alignment) {
+	table = CompTable{};
+	uint32_t col = 0, n_par = 0;
+	for (size_t i = 0; i < parts.size(); ++i) {
+		Part& p = parts[i];
+		const uint32_t a = i + 1 < parts.size() ? parts[i + 1].required_alignment() : std::max(alignment, 1u);
+		p.out_col = col;
+		p.width = (col + p.n_values + a - 1) / a * a - col;
+		col += p.width;
+		p.param_offset = n_par;
+		if (p.grid) {
+			p.grid->n_to_pad = p.width - p.n_values;
+			n_par += p.grid->n_params;
+		}
+	}
+	n_comp_params = n_par;
+	TCNN_CHECK(col <= COMP_MAX_WIDTH, "CompositeEncoding: encoded width " + std::to_string(col) + " exceeds " + std::to_string(COMP_MAX_WIDTH));
+	table.n_parts = (uint32_t)parts.size();
+	table.n_in = n_dims;
+	table.width = col;
+	std::vector<bool> read(n_dims, false);
+	for (size_t i = 0; i < parts.size(); ++i) {
+		const Part& p = parts[i];
+		CompPart& c = table.parts[i];
+		c.kind = p.kind;
+		c.in_col = p.in_col;
+		c.n_in = p.n_in;
+		c.out_col = p.out_col;
+		c.width = p.width;
+		c.n_values = p.n_values;
+		c.p0 = p.p0;
+		c.p1 = 0;
+		while (p.kind == COMP_ONEBLOB && (1u << c.p1) < p.p0) ++c.p1;
+		c.f0 = p.f0;
+		c.f1 = p.f1;
+		for (uint32_t d = 0; d < p.n_in; ++d) read[p.in_col + d] = true;
+		if (p.kind == COMP_GRID) {
+			for (uint32_t j = p.out_col; j < p.out_col + p.n_values; ++j) table.grid_cols[j / 32] |= 1u << (j % 32);
+			if (p.width > p.n_values) table.fwd_work = 1;
+			continue;
+		}
+		table.fwd_work = 1;
+		for (uint32_t d = 0; d < (p.kind == COMP_SH ? 1u : p.n_in); ++d) {
+			table.slot_part[table.n_slots] = (uint8_t)i;
+			table.slot_col[table.n_slots++] = (uint8_t)(p.in_col + d);
+		}
+	}
+	for (uint32_t c = 0; c < n_dims; ++c)
+		if (!read[c]) {
+			table.slot_part[table.n_slots] = (uint8_t)COMP_SLOT_ZERO;
+			table.slot_col[table.n_slots++] = (uint8_t)c;
+		}
+}
+
 uint32_t EncodingHost::n_output_unpadded() const {
 	switch (kind) {
 		case EncKind::OneBlob: return n_dims * n_bins;
 		case EncKind::Identity: return n_dims;
+		case EncKind::Composite: return table.width;  // composite.h:372-374: output_width() is the padded width
 		default: return grid->n_features;
 	}
 }
@@ -511,19 +681,51 @@ void EncodingHost::set_alignment(uint32_t a) {  // Encoding::set_alignment (enco
 		grid->set_alignment(a);
 		return;
 	}
+	if (kind == EncKind::Composite) {
+		layout(a);
+		return;
+	}
 	const uint32_t n = n_output_unpadded();
 	n_to_pad = (n + a - 1) / a * a - n;
 }
 
 void EncodingHost::initialize_params(Pcg32& rng, float* out, float s) const {
 	if (kind == EncKind::Grid) grid->initialize_params(rng, out, s);
+	// composite.h:422-427: the nested encodings in order, one generator
+	for (const Part& p : parts)
+		if (p.grid) p.grid->initialize_params(rng, out + p.param_offset, s);
+}
+
+json EncodingHost::Part::hyperparams() const {
+	switch (kind) {
+		case COMP_SH: return {{"otype", "SphericalHarmonics"}, {"degree", p0}};
+		case COMP_TRIANGLE: return {{"otype", "TriangleWave"}, {"n_frequencies", p0}};
+		case COMP_ONEBLOB: return {{"otype", "OneBlob"}, {"n_bins", p0}};
+		case COMP_IDENTITY: return {{"otype", "Identity"}, {"scale", f0}, {"offset", f1}};
+		default: return grid->hyperparams();
+	}
 }
 
 json EncodingHost::hyperparams() const {
 	switch (kind) {
 		case EncKind::OneBlob: return {{"otype", "OneBlob"}, {"n_bins", n_bins}};
 		case EncKind::Identity: return {{"otype", "Identity"}, {"scale", scale}, {"offset", offset}};
+		case EncKind::Composite: {
+			if (composite_otype != "Composite") return parts[0].hyperparams();
+			json nested = json::array();
+			for (const Part& p : parts) nested.push_back(p.hyperparams());
+			return {{"otype", "Composite"}, {"nested", nested}};  // composite.h:437-447
+		}
 		default: return grid->hyperparams();
+	}
+}
+
+std::string EncodingHost::name() const {
+	switch (kind) {
+		case EncKind::OneBlob: return "OneBlobEncoding";
+		case EncKind::Identity: return "IdentityEncoding";
+		case EncKind::Composite: return composite_otype + "Encoding";
+		default: return "GridEncoding";
 	}
 }
 
@@ -532,6 +734,18 @@ void EncodingHost::forward_aos(hipStream_t st, uint32_t B, const float* x, const
 	switch (kind) {
 		case EncKind::OneBlob: launch_oneblob_fwd(st, B, n_dims, n_bins, x, n_dims, out16, W, n_to_pad); break;
 		case EncKind::Identity: launch_identity_fwd(st, B, n_dims, scale, offset, x, n_dims, out16, W, n_to_pad); break;
+		case EncKind::Composite:
+			// one launch for every parameter-free value and all padding; each grid its own column slice
+			launch_composite_fwd(st, B, x, out16, table);
+			for (const Part& p : parts) {
+				if (!p.grid) continue;
+				const GridEncodingHost& g = *p.grid;
+				TCNN_CHECK(params16, "composite forward needs the nested grids' parameters");
+				launch_grid_fwd(st, g.desc.n_pos_dims, g.desc.n_features_per_level, g.desc.hash_type, B, g.desc.n_levels, x + p.in_col, n_dims,
+				                (const _Float16*)params16 + p.param_offset, (_Float16*)out16 + p.out_col, false, W, g.dev_levels(),
+				                g.hash_grid(), g.desc.interp, g.opts(), p.n_values);
+			}
+			break;
 		default:
 			if (grid->n_to_pad) TCNN_HIP_CHECK(hipMemsetAsync(out16, 0, (size_t)B * W * 2, st));
 			launch_grid_fwd(st, grid->desc.n_pos_dims, grid->desc.n_features_per_level, grid->desc.hash_type, B, grid->desc.n_levels, x,
@@ -546,12 +760,31 @@ void EncodingHost::backward_input(hipStream_t st, uint32_t B, const float* x, co
 	switch (kind) {
 		case EncKind::OneBlob: launch_oneblob_bwd(st, B, n_dims, n_bins, x, n_dims, dy16, W, dx, n_dims); break;
 		case EncKind::Identity: launch_identity_bwd(st, B, n_dims, scale, dy16, W, dx, n_dims); break;
+		case EncKind::Composite:
+			TCNN_CHECK(dy_layout == 2, "composite backward_input reads dL/d(encoding) as AoS rows");
+			launch_composite_bwd_input(st, B, x, dy16, W, dx, table);
+			for (const Part& p : parts) {
+				if (!p.grid) continue;
+				const GridEncodingHost& g = *p.grid;
+				TCNN_CHECK(params16, "grid backward_input needs the grid parameters");
+				launch_grid_bwd_input(st, g.desc.n_pos_dims, g.desc.n_features_per_level, g.desc.hash_type, B, g.desc.n_levels, x + p.in_col,
+				                      n_dims, (const _Float16*)params16 + p.param_offset, (const _Float16*)dy16 + p.out_col, 2, W,
+				                      dx + p.in_col, n_dims, g.dev_levels(), g.hash_grid(), g.desc.interp, g.opts());
+			}
+			break;
 		default:
 			TCNN_CHECK(params16, "grid backward_input needs the grid parameters");
 			launch_grid_bwd_input(st, grid->desc.n_pos_dims, grid->desc.n_features_per_level, grid->desc.hash_type, B, grid->desc.n_levels,
 			                      x, grid->desc.n_pos_dims, params16, dy16, dy_layout, W, dx, n_dims, grid->dev_levels(), grid->hash_grid(),
 			                      grid->desc.interp, grid->opts());
 	}
+}
+
+void EncodingHost::backward_params(hipStream_t st, uint32_t B, const float* x, const void* dy16, float* grad32) const {
+	const uint32_t W = padded_output_width();
+	for (const Part& p : parts)
+		if (p.grid)
+			p.grid->backward(st, *p.bufs, B, x + p.in_col, n_dims, (const _Float16*)dy16 + p.out_col, 2, W, grad32 + p.param_offset);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -861,6 +1094,7 @@ void NetworkHost::fwd_bwd_tile(hipStream_t st, StepWorkspace& ws, uint32_t B, co
 	const int dy_layout = pairs ? 0 : 2;
 	if (dL_dinput) enc->backward_input(st, B, pos, ws.delta0.p, dL_dinput, eparams, dy_layout);
 	if (grid) grid->backward(st, ws.gbw, B, pos, grid->desc.n_pos_dims, ws.delta0.p, dy_layout, IN, grad32 + n_mlp);
+	else enc->backward_params(st, B, pos, ws.delta0.p, grad32 + n_mlp);  // a composite's nested grids, each on its slice
 	if (mark) mark(2);
 	if (mark) mark(3);
 }
@@ -941,6 +1175,8 @@ void NetworkHost::fwd_bwd_layered(hipStream_t st, StepWorkspace& ws, uint32_t B,
 	if (enc_grad && dL_dinput) enc->backward_input(st, B, pos, denc, dL_dinput, eparams, dy_layout);
 	if (grid) {
 		grid->backward(st, ws.gbw, B, pos, grid->desc.n_pos_dims, denc, dy_layout, IN, grad32 + n_mlp);
+	} else if (enc_grad) {
+		enc->backward_params(st, B, pos, denc, grad32 + n_mlp);  // a composite's nested grids, each on its slice
 	}
 	if (mark) mark(2);
 	if (mark) mark(3);

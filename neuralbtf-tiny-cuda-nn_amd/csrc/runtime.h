@@ -199,8 +199,10 @@ struct AdamHost {
 };
 
 // Encodings of the network input (reference encodings/*.h): the multiresolution grid (parametric,
-// fused path), OneBlob (oneblob.h) and Identity (identity.h).
-enum class EncKind { Grid, OneBlob, Identity };
+// fused path), OneBlob (oneblob.h), Identity (identity.h), and Composite (composite.h, Concatenation):
+// a row of nested encodings, each over its own input columns. SphericalHarmonics and TriangleWave
+// exist as composite parts; standing alone they are a composite with one part (same kernels).
+enum class EncKind { Grid, OneBlob, Identity, Composite };
 
 struct EncodingHost {
 	EncKind kind = EncKind::Grid;
@@ -210,20 +212,53 @@ struct EncodingHost {
 	float scale = 1.0f, offset = 0.0f;  // Identity
 	uint32_t n_to_pad = 0;      // OneBlob / Identity padding (grid: grid->n_to_pad)
 
+	// Composite: the nested encodings in order. Widths follow composite.h:188-198: every part is
+	// created with alignment 1, part i is widened so that part i + 1 starts at a multiple of its
+	// required alignment (a grid's n_features_per_level, else 1), and the composite's own alignment
+	// widens the last part. Parameters are the nested grids' tables in order.
+	struct Part {
+		uint32_t kind = 0;  // COMP_* (kernels.h)
+		uint32_t in_col = 0, n_in = 0, out_col = 0, width = 0, n_values = 0;
+		uint32_t p0 = 0;             // SH degree | TriangleWave n_frequencies | OneBlob n_bins
+		float f0 = 1.0f, f1 = 0.0f;  // Identity scale, offset
+		uint32_t param_offset = 0;   // of a grid's table inside the encoding's parameters
+		std::unique_ptr<GridEncodingHost> grid;
+		std::unique_ptr<GridBwdBufs> bufs;  // scratch of this grid's backward
+		uint32_t required_alignment() const { return grid ? grid->desc.n_features_per_level : 1u; }
+		json hyperparams() const;
+	};
+	std::vector<Part> parts;
+	std::string composite_otype;  // "Composite", or the single part's own otype when it stands alone
+	CompTable table{};            // the parts as the kernels read them (layout())
+	uint32_t n_comp_params = 0;
+
 	EncodingHost(uint32_t n_dims_to_encode, const json& enc);
 	static bool known(const std::string& otype);
 	uint32_t n_output_unpadded() const;
-	uint32_t padded_output_width() const { return kind == EncKind::Grid ? grid->padded_output_width() : n_output_unpadded() + n_to_pad; }
+	uint32_t padded_output_width() const {
+		return kind == EncKind::Grid ? grid->padded_output_width() : kind == EncKind::Composite ? table.width : n_output_unpadded() + n_to_pad;
+	}
 	void set_alignment(uint32_t a);
-	uint32_t n_params() const { return kind == EncKind::Grid ? grid->n_params : 0u; }
+	uint32_t n_params() const { return kind == EncKind::Grid ? grid->n_params : kind == EncKind::Composite ? n_comp_params : 0u; }
 	void initialize_params(Pcg32& rng, float* host_out, float scale = 1.0f) const;
 	json hyperparams() const;
-	// encoded output AoS fp16 [B][padded_output_width()] (padding: grid 0, OneBlob / Identity 1)
+	// the reference's class name (SphericalHarmonicsEncoding, CompositeEncoding, ...)
+	std::string name() const;
+	// encoded output AoS fp16 [B][padded_output_width()] (padding: grid 0, OneBlob / Identity /
+	// TriangleWave 1 after the values, SphericalHarmonics 1 before them)
 	void forward_aos(hipStream_t st, uint32_t B, const float* x, const void* params16, void* out16) const;
 	// dL/dx fp32 [B][n_dims] from dL/d(encoding) fp16 AoS; params16 = the encoding's parameters (grid)
 	// dy16: AoS [B][padded width]; grid encodings also take dy_layout 0 (level-major pairs [L][B])
 	void backward_input(hipStream_t st, uint32_t B, const float* x, const void* dy16, float* dx, const void* params16 = nullptr,
 	                    int dy_layout = 2) const;
+	// Composite: the fp32 gradient of every nested grid's table from dL/d(encoding) AoS fp16
+	// [B][padded width], into grad32 [n_params()] (each grid's slice in nested order)
+	void backward_params(hipStream_t st, uint32_t B, const float* x, const void* dy16, float* grad32) const;
+
+private:
+	void parse_composite(const json& enc);
+	void add_part(uint32_t n_in, uint32_t in_col, const json& enc);
+	void layout(uint32_t alignment);  // widths, columns and the kernel table
 };
 
 // Workspace for one fwd/bwd over a batch of B (sizes grow only).

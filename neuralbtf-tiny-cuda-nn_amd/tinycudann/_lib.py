@@ -34,6 +34,7 @@ _SIGS = {
     "tcnn_create_network_with_input_encoding": (c_void_p, [c_uint32, c_uint32, c_char_p, c_char_p]),
     "tcnn_create_network": (c_void_p, [c_uint32, c_uint32, c_char_p]),
     "tcnn_create_encoding": (c_void_p, [c_uint32, c_char_p, c_int]),
+    "tcnn_create_encoding_aligned": (c_void_p, [c_uint32, c_char_p, c_int, c_uint32]),
     "tcnn_module_destroy": (None, [c_void_p]),
     "tcnn_module_inference": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p]),
     "tcnn_module_forward": (c_void_p, [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_int]),
