@@ -210,10 +210,9 @@ struct ModuleNWIE : ModuleBase {
 	std::string name() const override { return "NetworkWithInputEncoding"; }
 };
 
-// OneBlob, Identity and composite encodings (Composite, SphericalHarmonics, TriangleWave) as a module
-// (cpp_api.cu:145-149); a composite's nested grids make it own parameters and a gradient buffer.
-// Encoding modules take any batch size (per-point kernels with bounds checks, like the reference);
-// networks keep the 256 rule.
+// Every encoding as a module (cpp_api.cu:145-149); its grids make it own parameters and a gradient
+// buffer. Encoding modules take any batch size (per-point kernels with bounds checks, like the
+// reference); networks keep the 256 rule.
 struct ModuleEncoding : ModuleBase {
 	EncodingHost enc;
 	DevBuf grad32;
@@ -224,7 +223,7 @@ struct ModuleEncoding : ModuleBase {
 		enc.forward_aos(st, n, in, params, out);
 	}
 	std::unique_ptr<ModuleCtx> forward(hipStream_t st, uint32_t n, const float* in, void* out, const void* params, bool) override {
-		inference(st, n, in, out, params);
+		inference(st, n, in, out, params);  // nothing to keep: the backward recomputes dy/dx
 		return nullptr;
 	}
 	void backward(hipStream_t st, const ModuleCtx*, uint32_t n, float* dL_din, const void* dL_dout, void* dL_dparams, const float* in,
@@ -232,13 +231,29 @@ struct ModuleEncoding : ModuleBase {
 		if (dL_din) enc.backward_input(st, n, in, dL_dout, dL_din, params);
 		if (!dL_dparams || !enc.n_params()) return;
 		grad32.reserve((size_t)enc.n_params() * 4);
-		enc.backward_params(st, n, in, dL_dout, grad32.as<float>());
+		enc.backward_params(st, n, in, dL_dout, 2, grad32.as<float>());
 		launch_cast_f32_f16(st, grad32.as<float>(), dL_dparams, enc.n_params());
 	}
-	// (backward_backward_input: ModuleBase's "not implemented", for composites with grids too)
-	GridEncodingHost* grid_encoding() override {  // max_level of nested grids: not through the composite yet
-		if (enc.kind == EncKind::Composite) throw std::runtime_error(enc.name() + ": max_level is not implemented by the MI355X engine yet");
-		return nullptr;
+	// a grid standing alone; grids nested in a composite keep ModuleBase's "not implemented"
+	void backward_backward_input(hipStream_t st, uint32_t n, const float* dL_ddLdin, const float* in, const void* dL_dout,
+	                             void* dL_dparams, void* dL_ddLdout, float* dL_din, const void* params) override {
+		const GridEncodingHost* grid = enc.lone_grid();
+		if (!grid) return ModuleBase::backward_backward_input(st, n, dL_ddLdin, in, dL_dout, dL_dparams, dL_ddLdout, dL_din, params);
+		if (!dL_ddLdout && !dL_dparams) return;  // grid.h:913-915
+		TCNN_CHECK(params, "backward_backward_input needs the grid parameters");
+		if (dL_dparams) {
+			grad32.reserve((size_t)grid->n_params * 4);
+			TCNN_HIP_CHECK(hipMemsetAsync(grad32.p, 0, (size_t)grid->n_params * 4, st));  // GradientMode::Overwrite
+		}
+		const uint32_t W = enc.padded_output_width();
+		grid->backward_backward_input(st, n, in, enc.n_dims, params, dL_ddLdin, dL_dout, W, dL_dparams ? grad32.as<float>() : nullptr,
+		                              dL_ddLdout, W, dL_din);
+		if (dL_dparams) launch_cast_f32_f16(st, grad32.as<float>(), dL_dparams, grid->n_params);
+	}
+	// the lone grid (nullptr: a lone OneBlob / Identity); max_level does not go through the composite kernels yet
+	GridEncodingHost* grid_encoding() override {
+		if (!enc.lone_part()) throw std::runtime_error(enc.name() + ": max_level is not implemented by the MI355X engine yet");
+		return enc.lone_grid();
 	}
 	uint32_t n_input_dims() const override { return enc.n_dims; }
 	uint32_t n_output_dims() const override { return enc.padded_output_width(); }
@@ -252,61 +267,6 @@ struct ModuleEncoding : ModuleBase {
 	}
 	json hyperparams() const override { return enc.hyperparams(); }
 	std::string name() const override { return enc.name(); }
-};
-
-struct ModuleGrid : ModuleBase {
-	GridEncodingHost grid;
-	GridBwdBufs gbw;
-	DevBuf grad32;
-	ModuleGrid(uint32_t n_in, const json& enc) : grid(n_in, enc) {}
-	void inference(hipStream_t st, uint32_t n, const float* in, void* out, const void* params) override {
-		const uint32_t W = grid.padded_output_width();
-		if (grid.n_to_pad) TCNN_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)n * W * 2, st));
-		launch_grid_fwd(st, grid.desc.n_pos_dims, grid.desc.n_features_per_level, grid.desc.hash_type, n, grid.desc.n_levels,
-		                in, grid.desc.n_pos_dims, params, out, false, W, grid.dev_levels(), grid.hash_grid(), grid.desc.interp, grid.opts());
-	}
-	std::unique_ptr<ModuleCtx> forward(hipStream_t st, uint32_t n, const float* in, void* out, const void* params, bool prep) override {
-		(void)prep;  // dy/dx is recomputed in backward (launch_grid_bwd_input), nothing to keep
-		inference(st, n, in, out, params);
-		return nullptr;
-	}
-	void backward(hipStream_t st, const ModuleCtx*, uint32_t n, float* dL_din, const void* dL_dout, void* dL_dparams, const float* in,
-	              const void*, const void* params) override {
-		if (dL_din)
-			launch_grid_bwd_input(st, grid.desc.n_pos_dims, grid.desc.n_features_per_level, grid.desc.hash_type, n, grid.desc.n_levels, in,
-			                      grid.desc.n_pos_dims, params, dL_dout, 2, grid.padded_output_width(), dL_din, grid.desc.n_pos_dims,
-			                      grid.dev_levels(), grid.hash_grid(), grid.desc.interp, grid.opts());
-		if (!dL_dparams) return;
-		grad32.reserve((size_t)grid.n_params * 4);
-		grid.backward(st, gbw, n, in, grid.desc.n_pos_dims, dL_dout, 2, grid.padded_output_width(), grad32.as<float>());
-		launch_cast_f32_f16(st, grad32.as<float>(), dL_dparams, grid.n_params);
-	}
-	void backward_backward_input(hipStream_t st, uint32_t n, const float* dL_ddLdin, const float* in, const void* dL_dout,
-	                             void* dL_dparams, void* dL_ddLdout, float* dL_din, const void* params) override {
-		if (!dL_ddLdout && !dL_dparams) return;  // grid.h:913-915
-		TCNN_CHECK(params, "backward_backward_input needs the grid parameters");
-		if (dL_dparams) {
-			grad32.reserve((size_t)grid.n_params * 4);
-			TCNN_HIP_CHECK(hipMemsetAsync(grad32.p, 0, (size_t)grid.n_params * 4, st));  // GradientMode::Overwrite
-		}
-		const uint32_t W = grid.padded_output_width();
-		launch_grid_bwd_bwd(st, grid.desc.n_pos_dims, grid.desc.n_features_per_level, grid.desc.hash_type, n, grid.desc.n_levels, in,
-		                    grid.desc.n_pos_dims, params, dL_ddLdin, dL_dout, W, dL_dparams ? grad32.as<float>() : nullptr, dL_ddLdout, W,
-		                    dL_din, grid.dev_levels(), grid.hash_grid(), grid.desc.interp, grid.opts());
-		if (dL_dparams) launch_cast_f32_f16(st, grad32.as<float>(), dL_dparams, grid.n_params);
-	}
-	GridEncodingHost* grid_encoding() override { return &grid; }
-	uint32_t n_input_dims() const override { return grid.desc.n_pos_dims; }
-	uint32_t n_output_dims() const override { return grid.padded_output_width(); }
-	uint64_t n_params() const override { return grid.n_params; }
-	void initialize_params(uint64_t seed, float* p, float scale) override {
-		Pcg32 rng{seed};
-		std::vector<float> host(n_params());
-		grid.initialize_params(rng, host.data(), scale);
-		TCNN_HIP_CHECK(hipMemcpy(p, host.data(), host.size() * 4, hipMemcpyHostToDevice));
-	}
-	json hyperparams() const override { return grid.hyperparams(); }
-	std::string name() const override { return "GridEncoding"; }
 };
 }  // namespace
 
@@ -395,20 +355,16 @@ tcnn_module* tcnn_create_network(uint32_t n_in, uint32_t n_out, const char* net)
 }
 
 // create_encoding<T>(n_dims, encoding, alignment) (encoding.cu:131-145); alignment 0: none. A grid
-// standing alone keeps its own module and takes no alignment here.
+// standing alone takes no alignment here.
 tcnn_module* tcnn_create_encoding_aligned(uint32_t n_in, const char* enc, int precision, uint32_t alignment) {
 	return guard_ptr<tcnn_module>([&] {
 		TCNN_CHECK(precision == TCNN_PRECISION_FP16, "create_encoding: only Fp16 precision is implemented by the MI355X engine");
 		json j = parse_json(enc);
 		const std::string ot = j.is_object() && j.find("otype") != j.end() ? j["otype"].get<std::string>() : "OneBlob";
 		TCNN_CHECK(EncodingHost::known(ot), "Encoding '" + ot + "' is not implemented by the MI355X engine yet");
+		TCNN_CHECK(alignment == 0 || !EncodingHost::is_grid_otype(ot), "create_encoding: a grid encoding module takes no alignment");
 		auto r = std::make_unique<tcnn_module>();
-		const bool is_grid = ieq(ot, "HashGrid") || ieq(ot, "Grid") || ieq(ot, "TiledGrid") || ieq(ot, "DenseGrid");
-		if (!is_grid) r->m = std::make_unique<ModuleEncoding>(n_in, j, alignment);
-		else {
-			TCNN_CHECK(alignment == 0, "create_encoding: a grid encoding module takes no alignment");
-			r->m = std::make_unique<ModuleGrid>(n_in, j);
-		}
+		r->m = std::make_unique<ModuleEncoding>(n_in, j, alignment);
 		return r.release();
 	});
 }

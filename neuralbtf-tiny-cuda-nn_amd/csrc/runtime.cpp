@@ -375,6 +375,25 @@ void GridEncodingHost::backward(hipStream_t st, GridBwdBufs& w, uint32_t B, cons
 	reduce_items(st, w, grad32);
 }
 
+void GridEncodingHost::forward(hipStream_t st, uint32_t B, const float* pos, uint32_t pos_stride, const void* table16, void* out16,
+                               bool soa, uint32_t out_stride, uint32_t aos_row_cols) const {
+	launch_grid_fwd(st, desc.n_pos_dims, desc.n_features_per_level, desc.hash_type, B, desc.n_levels, pos, pos_stride, table16, out16, soa,
+	                out_stride, dev_levels(), hash_grid(), desc.interp, opts(), aos_row_cols);
+}
+
+void GridEncodingHost::backward_input(hipStream_t st, uint32_t B, const float* pos, uint32_t pos_stride, const void* table16,
+                                      const void* dy16, int dy_layout, uint32_t dy_stride, float* dx, uint32_t dx_stride) const {
+	launch_grid_bwd_input(st, desc.n_pos_dims, desc.n_features_per_level, desc.hash_type, B, desc.n_levels, pos, pos_stride, table16, dy16,
+	                      dy_layout, dy_stride, dx, dx_stride, dev_levels(), hash_grid(), desc.interp, opts());
+}
+
+void GridEncodingHost::backward_backward_input(hipStream_t st, uint32_t B, const float* pos, uint32_t pos_stride, const void* table16,
+                                               const float* dL_ddLdx, const void* dy16, uint32_t dy_stride, float* grad32,
+                                               void* dLddLdy16, uint32_t ddy_stride, float* dx) const {
+	launch_grid_bwd_bwd(st, desc.n_pos_dims, desc.n_features_per_level, desc.hash_type, B, desc.n_levels, pos, pos_stride, table16,
+	                    dL_ddLdx, dy16, dy_stride, grad32, dLddLdy16, ddy_stride, dx, dev_levels(), hash_grid(), desc.interp, opts());
+}
+
 static const char* grid_type_str(GridType t) { return t == GridType::Hash ? "Hash" : t == GridType::Dense ? "Dense" : "Tiled"; }
 static const char* hash_str(HashType t) { return t == HashType::Prime ? "Prime" : t == HashType::ReversedPrime ? "ReversedPrime" : "CoherentPrime"; }
 static const char* interp_str(Interp t) { return t == Interp::Nearest ? "Nearest" : t == Interp::Smoothstep ? "Smoothstep" : "Linear"; }
@@ -476,65 +495,31 @@ json AdamHost::hyperparams() const {
 // ------------------------------------------------------------------------------------------
 // Encodings (reference src/encoding.cu:77-150)
 // ------------------------------------------------------------------------------------------
-static bool is_grid_otype(const std::string& eo) {
+bool EncodingHost::is_grid_otype(const std::string& eo) {
 	return ieq(eo, "HashGrid") || ieq(eo, "Grid") || ieq(eo, "TiledGrid") || ieq(eo, "DenseGrid");
 }
-static bool is_composite_otype(const std::string& eo) {
-	return ieq(eo, "Composite") || ieq(eo, "NRC") || ieq(eo, "OneBlobFrequency") || ieq(eo, "SphericalHarmonics") ||
-	       ieq(eo, "TriangleWave");
-}
+static bool is_composite_otype(const std::string& eo) { return ieq(eo, "Composite") || ieq(eo, "NRC") || ieq(eo, "OneBlobFrequency"); }
 
 bool EncodingHost::known(const std::string& eo) {
-	return is_grid_otype(eo) || ieq(eo, "OneBlob") || ieq(eo, "Identity") || is_composite_otype(eo);
+	return is_grid_otype(eo) || ieq(eo, "OneBlob") || ieq(eo, "Identity") || ieq(eo, "SphericalHarmonics") || ieq(eo, "TriangleWave") ||
+	       is_composite_otype(eo);
 }
 
 EncodingHost::EncodingHost(uint32_t n_dims_to_encode, const json& enc) : n_dims(n_dims_to_encode) {
 	const std::string eo = jval<std::string>(enc, "otype", "OneBlob");  // encoding.cu:133
 	TCNN_CHECK(known(eo), "Encoding '" + eo + "' is not implemented by the MI355X engine yet");
-	if (ieq(eo, "OneBlob")) {
-		kind = EncKind::OneBlob;
-		n_bins = jval<uint32_t>(enc, "n_bins", 16u);  // encoding.cu:81-83
-		TCNN_CHECK(n_bins > 0 && (n_bins & (n_bins - 1)) == 0, "Number of bins must be a power of 2");
-	} else if (ieq(eo, "Identity")) {
-		kind = EncKind::Identity;
-		scale = jval<float>(enc, "scale", 1.0f);  // encoding.cu:77-79
-		offset = jval<float>(enc, "offset", 0.0f);
-	} else if (is_composite_otype(eo)) {
-		kind = EncKind::Composite;
-		if (ieq(eo, "Composite")) {
-			composite_otype = "Composite";
-			parse_composite(enc);
-		} else if (ieq(eo, "NRC") || ieq(eo, "OneBlobFrequency")) {  // encoding.cu:93-115
-			composite_otype = "Composite";
-			const json tri = {{"n_dims_to_encode", 3}, {"otype", "TriangleWave"}, {"n_frequencies", jval<uint32_t>(enc, "n_frequencies", 12u)}};
-			const json blob = {{"n_dims_to_encode", 5}, {"otype", "OneBlob"}, {"n_bins", jval<uint32_t>(enc, "n_bins", 4u)}};
-			const json rest = {{"otype", "Identity"}};
-			parse_composite(json{{"otype", "Composite"}, {"nested", json::array({tri, blob, rest})}});
-		} else {  // SphericalHarmonics / TriangleWave standing alone: one part over every input column
-			composite_otype = ieq(eo, "SphericalHarmonics") ? "SphericalHarmonics" : "TriangleWave";
-			add_part(n_dims_to_encode, 0, enc);
-		}
-		TCNN_CHECK(n_dims <= COMP_MAX_INPUTS, "CompositeEncoding: at most " + std::to_string(COMP_MAX_INPUTS) + " input dims");
-		TCNN_CHECK(parts.size() <= COMP_MAX_PARTS, "CompositeEncoding: at most " + std::to_string(COMP_MAX_PARTS) + " nested encodings");
-		// nested encodings that share an input column are refused: the reference's dL/dinput is then
-		// whatever the last of them wrote (order-dependent), and the plain stores here rely on it
-		std::vector<int> owner(n_dims, -1);
-		for (size_t i = 0; i < parts.size(); ++i) {
-			const Part& p = parts[i];
-			TCNN_CHECK(p.in_col + p.n_in <= n_dims, "CompositeEncoding: nested encoding " + std::to_string(i) + " reads input dims [" +
-			                                            std::to_string(p.in_col) + ", " + std::to_string(p.in_col + p.n_in) +
-			                                            ") beyond the composite's " + std::to_string(n_dims));
-			for (uint32_t c = p.in_col; c < p.in_col + p.n_in; ++c) {
-				TCNN_CHECK(owner[c] < 0, "CompositeEncoding: nested encodings " + std::to_string(owner[c]) + " and " + std::to_string(i) +
-				                             " overlap in input dim " + std::to_string(c) + "; overlapping ranges are not supported");
-				owner[c] = (int)i;
-			}
-		}
-		layout(1);
-	} else {
-		kind = EncKind::Grid;
-		grid = std::make_unique<GridEncodingHost>(n_dims_to_encode, enc);
+	if (ieq(eo, "Composite")) {
+		parse_composite(enc);
+	} else if (is_composite_otype(eo)) {  // NRC / OneBlobFrequency, encoding.cu:93-115
+		const json tri = {{"n_dims_to_encode", 3}, {"otype", "TriangleWave"}, {"n_frequencies", jval<uint32_t>(enc, "n_frequencies", 12u)}};
+		const json blob = {{"n_dims_to_encode", 5}, {"otype", "OneBlob"}, {"n_bins", jval<uint32_t>(enc, "n_bins", 4u)}};
+		const json rest = {{"otype", "Identity"}};
+		parse_composite(json{{"otype", "Composite"}, {"nested", json::array({tri, blob, rest})}});
+	} else {  // standing alone: one part over every input column
+		add_part(n_dims_to_encode, 0, enc);
 	}
+	otype = is_composite_otype(eo) ? "Composite" : parts[0].hyperparams()["otype"].get<std::string>();
+	layout(1);
 }
 
 // CompositeEncoding::CompositeEncoding (composite.h:138-186)
@@ -570,6 +555,20 @@ void EncodingHost::parse_composite(const json& enc) {
 		}
 		if (n > 0) add_part(n, off, nested[i]);
 		off += n;
+	}
+	// nested encodings that share an input column are refused: the reference's dL/dinput is then
+	// whatever the last of them wrote (order-dependent), and the plain stores here rely on it
+	std::vector<int> owner(n_dims, -1);
+	for (size_t i = 0; i < parts.size(); ++i) {
+		const Part& p = parts[i];
+		TCNN_CHECK(p.in_col + p.n_in <= n_dims, "CompositeEncoding: nested encoding " + std::to_string(i) + " reads input dims [" +
+		                                            std::to_string(p.in_col) + ", " + std::to_string(p.in_col + p.n_in) +
+		                                            ") beyond the composite's " + std::to_string(n_dims));
+		for (uint32_t c = p.in_col; c < p.in_col + p.n_in; ++c) {
+			TCNN_CHECK(owner[c] < 0, "CompositeEncoding: nested encodings " + std::to_string(owner[c]) + " and " + std::to_string(i) +
+			                             " overlap in input dim " + std::to_string(c) + "; overlapping ranges are not supported");
+			owner[c] = (int)i;
+		}
 	}
 }
 
@@ -614,7 +613,6 @@ void EncodingHost::add_part(uint32_t n_in, uint32_t in_col, const json& enc) {
 // composite.h:188-198 (each part's output alignment), then Encoding::set_alignment on the composite
 // (encoding.h:70, composite.h:380-384: the last part takes the rest)
 void EncodingHost::layout(uint32_t alignment) {
-	table = CompTable{};
 	uint32_t col = 0, n_par = 0;
 	for (size_t i = 0; i < parts.size(); ++i) {
 		Part& p = parts[i];
@@ -628,11 +626,21 @@ void EncodingHost::layout(uint32_t alignment) {
 			n_par += p.grid->n_params;
 		}
 	}
-	n_comp_params = n_par;
-	TCNN_CHECK(col <= COMP_MAX_WIDTH, "CompositeEncoding: encoded width " + std::to_string(col) + " exceeds " + std::to_string(COMP_MAX_WIDTH));
+	n_grid_params = n_par;
+	if (!lone_part()) build_table();
+}
+
+// The limits are the table's (a kernel argument, and LDS rows of `width`): they do not bind a part
+// that stands alone with its own kernel.
+void EncodingHost::build_table() {
+	const uint32_t width = padded_output_width();
+	TCNN_CHECK(n_dims <= COMP_MAX_INPUTS, "CompositeEncoding: at most " + std::to_string(COMP_MAX_INPUTS) + " input dims");
+	TCNN_CHECK(parts.size() <= COMP_MAX_PARTS, "CompositeEncoding: at most " + std::to_string(COMP_MAX_PARTS) + " nested encodings");
+	TCNN_CHECK(width <= COMP_MAX_WIDTH, "CompositeEncoding: encoded width " + std::to_string(width) + " exceeds " + std::to_string(COMP_MAX_WIDTH));
+	table = CompTable{};
 	table.n_parts = (uint32_t)parts.size();
 	table.n_in = n_dims;
-	table.width = col;
+	table.width = width;
 	std::vector<bool> read(n_dims, false);
 	for (size_t i = 0; i < parts.size(); ++i) {
 		const Part& p = parts[i];
@@ -667,30 +675,7 @@ void EncodingHost::layout(uint32_t alignment) {
 		}
 }
 
-uint32_t EncodingHost::n_output_unpadded() const {
-	switch (kind) {
-		case EncKind::OneBlob: return n_dims * n_bins;
-		case EncKind::Identity: return n_dims;
-		case EncKind::Composite: return table.width;  // composite.h:372-374: output_width() is the padded width
-		default: return grid->n_features;
-	}
-}
-
-void EncodingHost::set_alignment(uint32_t a) {  // Encoding::set_alignment (encoding.h)
-	if (kind == EncKind::Grid) {
-		grid->set_alignment(a);
-		return;
-	}
-	if (kind == EncKind::Composite) {
-		layout(a);
-		return;
-	}
-	const uint32_t n = n_output_unpadded();
-	n_to_pad = (n + a - 1) / a * a - n;
-}
-
 void EncodingHost::initialize_params(Pcg32& rng, float* out, float s) const {
-	if (kind == EncKind::Grid) grid->initialize_params(rng, out, s);
 	// composite.h:422-427: the nested encodings in order, one generator
 	for (const Part& p : parts)
 		if (p.grid) p.grid->initialize_params(rng, out + p.param_offset, s);
@@ -707,84 +692,58 @@ json EncodingHost::Part::hyperparams() const {
 }
 
 json EncodingHost::hyperparams() const {
-	switch (kind) {
-		case EncKind::OneBlob: return {{"otype", "OneBlob"}, {"n_bins", n_bins}};
-		case EncKind::Identity: return {{"otype", "Identity"}, {"scale", scale}, {"offset", offset}};
-		case EncKind::Composite: {
-			if (composite_otype != "Composite") return parts[0].hyperparams();
-			json nested = json::array();
-			for (const Part& p : parts) nested.push_back(p.hyperparams());
-			return {{"otype", "Composite"}, {"nested", nested}};  // composite.h:437-447
-		}
-		default: return grid->hyperparams();
-	}
+	if (otype != "Composite") return parts[0].hyperparams();
+	json nested = json::array();
+	for (const Part& p : parts) nested.push_back(p.hyperparams());
+	return {{"otype", "Composite"}, {"nested", nested}};  // composite.h:437-447
 }
 
-std::string EncodingHost::name() const {
-	switch (kind) {
-		case EncKind::OneBlob: return "OneBlobEncoding";
-		case EncKind::Identity: return "IdentityEncoding";
-		case EncKind::Composite: return composite_otype + "Encoding";
-		default: return "GridEncoding";
-	}
+void EncodingHost::Part::forward(hipStream_t st, uint32_t B, const float* x, uint32_t x_stride, const void* params16, void* out16,
+                                 uint32_t stride, bool alone) const {
+	_Float16* out = (_Float16*)out16 + out_col;
+	if (kind == COMP_ONEBLOB) return launch_oneblob_fwd(st, B, n_in, p0, x + in_col, x_stride, out, stride, width - n_values);
+	if (kind == COMP_IDENTITY) return launch_identity_fwd(st, B, n_in, f0, f1, x + in_col, x_stride, out, stride, width - n_values);
+	TCNN_CHECK(kind == COMP_GRID, "this encoding has no kernel of its own");
+	TCNN_CHECK(params16, "grid forward needs the grid parameters");
+	if (alone && width > n_values) TCNN_HIP_CHECK(hipMemsetAsync(out16, 0, (size_t)B * stride * 2, st));
+	grid->forward(st, B, x + in_col, x_stride, (const _Float16*)params16 + param_offset, out, false, stride, alone ? 0u : n_values);
+}
+
+void EncodingHost::Part::backward_input(hipStream_t st, uint32_t B, const float* x, uint32_t x_stride, const void* params16,
+                                        const void* dy16, int dy_layout, uint32_t stride, float* dx) const {
+	const _Float16* dy = (const _Float16*)dy16 + out_col;
+	if (kind == COMP_ONEBLOB) return launch_oneblob_bwd(st, B, n_in, p0, x + in_col, x_stride, dy, stride, dx + in_col, x_stride);
+	if (kind == COMP_IDENTITY) return launch_identity_bwd(st, B, n_in, f0, dy, stride, dx + in_col, x_stride);
+	TCNN_CHECK(kind == COMP_GRID, "this encoding has no kernel of its own");
+	TCNN_CHECK(params16, "grid backward_input needs the grid parameters");
+	grid->backward_input(st, B, x + in_col, x_stride, (const _Float16*)params16 + param_offset, dy, dy_layout, stride, dx + in_col, x_stride);
 }
 
 void EncodingHost::forward_aos(hipStream_t st, uint32_t B, const float* x, const void* params16, void* out16) const {
 	const uint32_t W = padded_output_width();
-	switch (kind) {
-		case EncKind::OneBlob: launch_oneblob_fwd(st, B, n_dims, n_bins, x, n_dims, out16, W, n_to_pad); break;
-		case EncKind::Identity: launch_identity_fwd(st, B, n_dims, scale, offset, x, n_dims, out16, W, n_to_pad); break;
-		case EncKind::Composite:
-			// one launch for every parameter-free value and all padding; each grid its own column slice
-			launch_composite_fwd(st, B, x, out16, table);
-			for (const Part& p : parts) {
-				if (!p.grid) continue;
-				const GridEncodingHost& g = *p.grid;
-				TCNN_CHECK(params16, "composite forward needs the nested grids' parameters");
-				launch_grid_fwd(st, g.desc.n_pos_dims, g.desc.n_features_per_level, g.desc.hash_type, B, g.desc.n_levels, x + p.in_col, n_dims,
-				                (const _Float16*)params16 + p.param_offset, (_Float16*)out16 + p.out_col, false, W, g.dev_levels(),
-				                g.hash_grid(), g.desc.interp, g.opts(), p.n_values);
-			}
-			break;
-		default:
-			if (grid->n_to_pad) TCNN_HIP_CHECK(hipMemsetAsync(out16, 0, (size_t)B * W * 2, st));
-			launch_grid_fwd(st, grid->desc.n_pos_dims, grid->desc.n_features_per_level, grid->desc.hash_type, B, grid->desc.n_levels, x,
-			                grid->desc.n_pos_dims, params16, out16, false, W, grid->dev_levels(), grid->hash_grid(), grid->desc.interp,
-			                grid->opts());
-	}
+	if (const Part* p = lone_part()) return p->forward(st, B, x, n_dims, params16, out16, W, true);
+	// one launch for every parameter-free value and all padding; each grid its own column slice
+	launch_composite_fwd(st, B, x, out16, table);
+	for (const Part& p : parts)
+		if (p.grid) p.forward(st, B, x, n_dims, params16, out16, W, false);
 }
 
 void EncodingHost::backward_input(hipStream_t st, uint32_t B, const float* x, const void* dy16, float* dx, const void* params16,
                                   int dy_layout) const {
 	const uint32_t W = padded_output_width();
-	switch (kind) {
-		case EncKind::OneBlob: launch_oneblob_bwd(st, B, n_dims, n_bins, x, n_dims, dy16, W, dx, n_dims); break;
-		case EncKind::Identity: launch_identity_bwd(st, B, n_dims, scale, dy16, W, dx, n_dims); break;
-		case EncKind::Composite:
-			TCNN_CHECK(dy_layout == 2, "composite backward_input reads dL/d(encoding) as AoS rows");
-			launch_composite_bwd_input(st, B, x, dy16, W, dx, table);
-			for (const Part& p : parts) {
-				if (!p.grid) continue;
-				const GridEncodingHost& g = *p.grid;
-				TCNN_CHECK(params16, "grid backward_input needs the grid parameters");
-				launch_grid_bwd_input(st, g.desc.n_pos_dims, g.desc.n_features_per_level, g.desc.hash_type, B, g.desc.n_levels, x + p.in_col,
-				                      n_dims, (const _Float16*)params16 + p.param_offset, (const _Float16*)dy16 + p.out_col, 2, W,
-				                      dx + p.in_col, n_dims, g.dev_levels(), g.hash_grid(), g.desc.interp, g.opts());
-			}
-			break;
-		default:
-			TCNN_CHECK(params16, "grid backward_input needs the grid parameters");
-			launch_grid_bwd_input(st, grid->desc.n_pos_dims, grid->desc.n_features_per_level, grid->desc.hash_type, B, grid->desc.n_levels,
-			                      x, grid->desc.n_pos_dims, params16, dy16, dy_layout, W, dx, n_dims, grid->dev_levels(), grid->hash_grid(),
-			                      grid->desc.interp, grid->opts());
-	}
+	TCNN_CHECK(dy_layout == 2 || lone_grid(), "backward_input reads dL/d(encoding) as AoS rows");
+	if (const Part* p = lone_part()) return p->backward_input(st, B, x, n_dims, params16, dy16, dy_layout, W, dx);
+	launch_composite_bwd_input(st, B, x, dy16, W, dx, table);
+	for (const Part& p : parts)
+		if (p.grid) p.backward_input(st, B, x, n_dims, params16, dy16, 2, W, dx);
 }
 
-void EncodingHost::backward_params(hipStream_t st, uint32_t B, const float* x, const void* dy16, float* grad32) const {
+void EncodingHost::backward_params(hipStream_t st, uint32_t B, const float* x, const void* dy16, int dy_layout, float* grad32) const {
 	const uint32_t W = padded_output_width();
+	TCNN_CHECK(dy_layout == 2 || lone_grid(), "backward_params reads dL/d(encoding) as AoS rows");
 	for (const Part& p : parts)
 		if (p.grid)
-			p.grid->backward(st, *p.bufs, B, x + p.in_col, n_dims, (const _Float16*)dy16 + p.out_col, 2, W, grad32 + p.param_offset);
+			p.grid->backward(st, *p.bufs, B, x + p.in_col, n_dims, (const _Float16*)dy16 + p.out_col, dy_layout, W, grad32 + p.param_offset);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -792,7 +751,7 @@ void EncodingHost::backward_params(hipStream_t st, uint32_t B, const float* x, c
 // ------------------------------------------------------------------------------------------
 NetworkHost::NetworkHost(uint32_t n_in, uint32_t n_out, const json& e, const json& net) : n_input_dims(n_in), n_output_dims(n_out) {
 	enc = std::make_unique<EncodingHost>(n_in, e);
-	grid = enc->grid.get();
+	grid = enc->lone_grid();
 	enc->set_alignment(16);  // minimum_alignment(network): 16 for FullyFusedMLP and CutlassMLP (network.cu:76-95)
 	mlp = MlpHost(enc->padded_output_width(), n_out, net);
 	TCNN_CHECK(fused_ok() || layered_ok(), "network shape (n_neurons = " + std::to_string(mlp.width) + ", input width " +
@@ -866,7 +825,7 @@ void NetworkHost::inference(hipStream_t st, StepWorkspace& ws, uint32_t B, const
                             bool trust_image) {
 	TCNN_CHECK(B % 32 == 0, "inference: batch must be a multiple of 32");
 	const uint32_t IN = mlp.n_input;
-	const uint8_t* eparams = (const uint8_t*)params16 + (size_t)mlp.n_params() * 2;
+	const void* eparams = enc_params(params16);
 	if (fused_ok() && mlp_infer_supported(mlp.width, IN, mlp.n_hidden_layers, mlp.padded_output, mlp.activation)) {
 		// the trainer's packed image when it matches its parameters, else the kernel builds its LDS
 		// image from the parameters themselves (no pack launch)
@@ -890,7 +849,7 @@ void NetworkHost::inference(hipStream_t st, StepWorkspace& ws, uint32_t B, const
 void NetworkHost::fused_forward(hipStream_t st, StepWorkspace& ws, uint32_t B, const float* pos, const void* params16, bool use_image,
                                 void* enc_soa, void* out16) {
 	const uint32_t IN = mlp.n_input;
-	const uint8_t* eparams = (const uint8_t*)params16 + (size_t)mlp.n_params() * 2;
+	const void* eparams = enc_params(params16);
 	if (sw.split_forward) {
 		if (!use_image) {
 			ws.wimage.reserve(fused_weight_image_bytes(mlp.width, IN, mlp.n_hidden_layers));
@@ -902,9 +861,7 @@ void NetworkHost::fused_forward(hipStream_t st, StepWorkspace& ws, uint32_t B, c
 			ws.enc16.reserve((size_t)IN * B * 2);
 			enc = ws.enc16.p;
 		}
-		launch_grid_fwd(st, grid->desc.n_pos_dims, grid->desc.n_features_per_level, grid->desc.hash_type, B, grid->desc.n_levels, pos,
-		                grid->desc.n_pos_dims, eparams, enc, true, 0, grid->dev_levels(), grid->hash_grid(), grid->desc.interp,
-		                grid->opts());
+		grid->forward(st, B, pos, grid->desc.n_pos_dims, eparams, enc, true, 0);
 		launch_mlp_infer(st, mlp.width, IN, mlp.n_hidden_layers, mlp.activation, true, B, ws.wimage.p, enc, out16);
 		return;
 	}
@@ -931,7 +888,7 @@ int NetworkHost::forward_keep(hipStream_t st, StepWorkspace& ws, uint32_t B, con
                               bool with_dinput, DevBuf& keep) {
 	const int layout = backward_engine_keep(with_dinput);
 	const uint32_t IN = mlp.n_input;
-	const uint8_t* eparams = (const uint8_t*)params16 + (size_t)mlp.n_params() * 2;
+	const void* eparams = enc_params(params16);
 	if (layout == KEEP_FUSED_SOA && mlp_infer_supported(mlp.width, IN, mlp.n_hidden_layers, mlp.padded_output, mlp.activation)) {
 		keep.reserve((size_t)IN * B * 2);
 		fused_forward(st, ws, B, pos, params16, false, keep.p, out16);
@@ -987,9 +944,8 @@ void NetworkHost::fused_kernel(hipStream_t st, StepWorkspace& ws, uint32_t B, co
 		ws.wimage_valid = false;
 		use_image = true;
 	}
-	const uint8_t* table = (const uint8_t*)params16 + (size_t)n_mlp * 2;
 	launch_fused_train(st, mlp.width, mlp.n_input, mlp.n_hidden_layers, grid->desc.n_pos_dims, grid->desc.hash_type,
-	                   mlp.activation, B, dims, loss_scale, params16, table, pos, target, out16, ws.dLdenc.p,
+	                   mlp.activation, B, dims, loss_scale, params16, enc_params(params16), pos, target, out16, ws.dLdenc.p,
 	                   ws.wgrad_partial.as<float>(), ws.loss_partial.as<float>(), grid->dev_levels(), grid->hash_grid(),
 	                   grid->desc.interp, nb, dout16, use_image ? ws.wimage.p : nullptr, loss_l2,
 	                   grid->inrange_index_ok && grid->desc.interp == Interp::Linear && !sw.no_inrange_index, enc_soa,
@@ -1055,7 +1011,7 @@ void NetworkHost::fwd_bwd_tile(hipStream_t st, StepWorkspace& ws, uint32_t B, co
 	TCNN_CHECK(B % 32 == 0, "training: batch must be a multiple of 32");
 	const uint32_t W = mlp.width, IN = mlp.n_input, NH = mlp.n_hidden_layers;
 	const uint32_t n_mlp = mlp.n_params();
-	const uint8_t* eparams = (const uint8_t*)params16 + (size_t)n_mlp * 2;
+	const void* eparams = enc_params(params16);
 	// configs[3]-shaped networks gather the grid encoding inside the tile kernel (no AoS pass)
 	TileGridEnc genc{};
 	const bool in_kernel = !enc_aos && grid && grid->desc.n_pos_dims == 2 && grid->desc.n_features_per_level == 2 &&
@@ -1077,24 +1033,21 @@ void NetworkHost::fwd_bwd_tile(hipStream_t st, StepWorkspace& ws, uint32_t B, co
 	ws.wgrad_partial.reserve((size_t)nb * n_mlp * 4);
 	ws.loss_partial.reserve((size_t)nb * 4);
 	const bool enc_grad = enc->n_params() > 0 || dL_dinput;
-	// a grid with feature pairs and no padding takes dL/d(encoding) as level-major pairs [L][B]
-	const bool pairs = grid && grid->desc.n_features_per_level == 2 && grid->n_to_pad == 0;
+	const int dy_layout = enc->dy_layout();
 	if (enc_grad) ws.delta0.reserve((size_t)B * IN * 2);
 	const uint32_t wT_bytes = tile_train_wT_bytes(W, IN, NH);
 	if (wT_bytes) ws.tile_wT.reserve(wT_bytes);
 	launch_mlp_tile_train(st, W, IN, NH, mlp.activation, mlp.output_activation, B, dims, loss_scale, loss_l2, params16, enc_aos, target,
 	                      dout16, out16,
-	                      enc_grad ? ws.delta0.p : nullptr, pairs ? 1 : 0, ws.wgrad_partial.as<float>(), ws.loss_partial.as<float>(),
+	                      enc_grad ? ws.delta0.p : nullptr, dy_layout == 0 ? 1 : 0, ws.wgrad_partial.as<float>(), ws.loss_partial.as<float>(),
 	                      wT_bytes ? ws.tile_wT.p : nullptr, in_kernel ? &genc : nullptr);
 	ws.n_loss_partials = dout16 ? 0 : nb;
 	const size_t tf = reduce_partials_tmp_floats(nb, n_mlp);
 	if (tf) ws.red_tmp.reserve(tf * 4);
 	launch_reduce_partials(st, ws.wgrad_partial.as<float>(), nb, n_mlp, n_mlp, grad32, ws.red_tmp.as<float>());
 	if (mark) mark(1);
-	const int dy_layout = pairs ? 0 : 2;
 	if (dL_dinput) enc->backward_input(st, B, pos, ws.delta0.p, dL_dinput, eparams, dy_layout);
-	if (grid) grid->backward(st, ws.gbw, B, pos, grid->desc.n_pos_dims, ws.delta0.p, dy_layout, IN, grad32 + n_mlp);
-	else enc->backward_params(st, B, pos, ws.delta0.p, grad32 + n_mlp);  // a composite's nested grids, each on its slice
+	enc->backward_params(st, B, pos, ws.delta0.p, dy_layout, grad32 + n_mlp);
 	if (mark) mark(2);
 	if (mark) mark(3);
 }
@@ -1109,7 +1062,7 @@ void NetworkHost::fwd_bwd_layered(hipStream_t st, StepWorkspace& ws, uint32_t B,
 	const uint32_t W = mlp.width, IN = mlp.n_input, NH = mlp.n_hidden_layers, OUTP = mlp.padded_output;
 	const uint32_t n_mlp = mlp.n_params();
 	const _Float16* p16 = (const _Float16*)params16;
-	const uint8_t* eparams = (const uint8_t*)params16 + (size_t)n_mlp * 2;
+	const void* eparams = enc_params(params16);
 	const uint32_t nck = wgrad_n_chunks(B);
 	const uint32_t maxK = std::max(W, IN);
 	ws.enc16.reserve((size_t)B * IN * 2);
@@ -1148,10 +1101,8 @@ void NetworkHost::fwd_bwd_layered(hipStream_t st, StepWorkspace& ws, uint32_t B,
 	_Float16* dcur = ws.delta0.as<_Float16>();
 	_Float16* dnext = ws.delta1.as<_Float16>();
 	const bool enc_grad = enc->n_params() > 0 || dL_dinput;
-	// a grid with feature pairs and no padding takes dL/d(encoding) as level-major pairs [L][B], the
-	// layout its backward reads coalesced (AoS rows would cost one 64-byte line per 4-byte read)
-	const bool pairs = grid && grid->desc.n_features_per_level == 2 && grid->n_to_pad == 0;
-	const int dy_layout = pairs ? 0 : 2;
+	const int dy_layout = enc->dy_layout();
+	const bool pairs = dy_layout == 0;
 	const _Float16* denc = dnext;  // dL/d(encoding), when enc_grad
 	if (NH == 0) {  // one matrix: dWout = dout^T enc, dL/d(encoding) = Wout^T dout (no transfer)
 		wgrad(OUTP, IN, ws.dout16.p, ws.enc16.p, 0);
@@ -1172,12 +1123,8 @@ void NetworkHost::fwd_bwd_layered(hipStream_t st, StepWorkspace& ws, uint32_t B,
 		if (enc_grad) launch_layer_bwd(st, B, W, IN, p16, dcur, nullptr, dnext, ACT_NONE, pairs);
 		denc = dnext;
 	}
-	if (enc_grad && dL_dinput) enc->backward_input(st, B, pos, denc, dL_dinput, eparams, dy_layout);
-	if (grid) {
-		grid->backward(st, ws.gbw, B, pos, grid->desc.n_pos_dims, denc, dy_layout, IN, grad32 + n_mlp);
-	} else if (enc_grad) {
-		enc->backward_params(st, B, pos, denc, grad32 + n_mlp);  // a composite's nested grids, each on its slice
-	}
+	if (dL_dinput) enc->backward_input(st, B, pos, denc, dL_dinput, eparams, dy_layout);
+	enc->backward_params(st, B, pos, denc, dy_layout, grad32 + n_mlp);
 	if (mark) mark(2);
 	if (mark) mark(3);
 }
@@ -1304,10 +1251,8 @@ void TrainerHost::training_step_overlapped(hipStream_t st, uint32_t B, const flo
 	mark(st, 0);
 	const void* enc_soa = nullptr;
 	if (m.sw.split_encode) {  // A/B experiment: the encoding as its own pass, read by the fused kernel
-		const GridEncodingHost& g = *m.grid;
 		ws.enc16.reserve((size_t)m.mlp.n_input * B * 2);
-		launch_grid_fwd(st, g.desc.n_pos_dims, g.desc.n_features_per_level, g.desc.hash_type, B, g.desc.n_levels, input, g.desc.n_pos_dims,
-		                (const uint8_t*)w16.p + n_mlp * 2, ws.enc16.p, true, 0, g.dev_levels(), g.hash_grid(), g.desc.interp, g.opts());
+		m.grid->forward(st, B, input, m.grid->desc.n_pos_dims, m.enc_params(w16.p), ws.enc16.p, true, 0);
 		enc_soa = ws.enc16.p;
 	}
 	m.fused_kernel(st, ws, B, input, target, n_output_dims, loss_scale, w16.p, false, nullptr, nullptr, enc_soa);

@@ -173,6 +173,15 @@ struct GridEncodingHost {
 	void reduce_items(hipStream_t st, GridBwdBufs& w, float* grad32, GradFinalize fin = {}) const;
 	void backward(hipStream_t st, GridBwdBufs& w, uint32_t B, const float* pos, uint32_t pstride, const void* dy, int layout,
 	              uint32_t dy_stride, float* grad32) const;
+	// launch_grid_fwd / launch_grid_bwd_input / launch_grid_bwd_bwd (kernels.h) with this grid's
+	// shape, level table and options filled in
+	void forward(hipStream_t st, uint32_t B, const float* pos, uint32_t pos_stride, const void* table16, void* out16, bool soa,
+	             uint32_t out_stride, uint32_t aos_row_cols = 0) const;
+	void backward_input(hipStream_t st, uint32_t B, const float* pos, uint32_t pos_stride, const void* table16, const void* dy16,
+	                    int dy_layout, uint32_t dy_stride, float* dx, uint32_t dx_stride) const;
+	void backward_backward_input(hipStream_t st, uint32_t B, const float* pos, uint32_t pos_stride, const void* table16,
+	                             const float* dL_ddLdx, const void* dy16, uint32_t dy_stride, float* grad32, void* dLddLdy16,
+	                             uint32_t ddy_stride, float* dx) const;
 };
 
 // ---- fully fused MLP shape (reference networks/fully_fused_mlp.h) ----
@@ -198,24 +207,19 @@ struct AdamHost {
 	json hyperparams() const;
 };
 
-// Encodings of the network input (reference encodings/*.h): the multiresolution grid (parametric,
-// fused path), OneBlob (oneblob.h), Identity (identity.h), and Composite (composite.h, Concatenation):
-// a row of nested encodings, each over its own input columns. SphericalHarmonics and TriangleWave
-// exist as composite parts; standing alone they are a composite with one part (same kernels).
-enum class EncKind { Grid, OneBlob, Identity, Composite };
-
+// Encodings of the network input (reference encodings/*.h). An encoding is its list of parts, each
+// over its own input columns (composite.h, Concatenation): the multiresolution grid (parametric),
+// OneBlob (oneblob.h), Identity (identity.h), SphericalHarmonics and TriangleWave. An encoding that is
+// not spelled as a Composite is one part over every input column. Grid, OneBlob and Identity parts
+// have kernels of their own, which a part that stands alone runs (rows of any width); every other
+// encoding runs the composite kernels (composite.hip), then each nested grid on its column slice.
 struct EncodingHost {
-	EncKind kind = EncKind::Grid;
-	std::unique_ptr<GridEncodingHost> grid;
-	uint32_t n_dims = 0;        // input dims encoded
-	uint32_t n_bins = 16;       // OneBlob
-	float scale = 1.0f, offset = 0.0f;  // Identity
-	uint32_t n_to_pad = 0;      // OneBlob / Identity padding (grid: grid->n_to_pad)
+	uint32_t n_dims = 0;  // input dims encoded
 
-	// Composite: the nested encodings in order. Widths follow composite.h:188-198: every part is
-	// created with alignment 1, part i is widened so that part i + 1 starts at a multiple of its
-	// required alignment (a grid's n_features_per_level, else 1), and the composite's own alignment
-	// widens the last part. Parameters are the nested grids' tables in order.
+	// Widths follow composite.h:188-198: every part is created with alignment 1, part i is widened so
+	// that part i + 1 starts at a multiple of its required alignment (a grid's n_features_per_level,
+	// else 1), and the encoding's own alignment widens the last part. Parameters are the grids' tables
+	// in order.
 	struct Part {
 		uint32_t kind = 0;  // COMP_* (kernels.h)
 		uint32_t in_col = 0, n_in = 0, out_col = 0, width = 0, n_values = 0;
@@ -225,40 +229,57 @@ struct EncodingHost {
 		std::unique_ptr<GridEncodingHost> grid;
 		std::unique_ptr<GridBwdBufs> bufs;  // scratch of this grid's backward
 		uint32_t required_alignment() const { return grid ? grid->desc.n_features_per_level : 1u; }
+		bool own_kernel() const { return kind == COMP_GRID || kind == COMP_ONEBLOB || kind == COMP_IDENTITY; }
 		json hyperparams() const;
+		// This part's own kernel on its column slice. x, params16, out16 / dy16 and dx are the
+		// encoding's: fp32 [B][x_stride], the parameters, AoS fp16 rows of `stride` columns, fp32
+		// [B][x_stride]. alone: the part owns the whole row (a grid then zeroes it for its padding).
+		void forward(hipStream_t st, uint32_t B, const float* x, uint32_t x_stride, const void* params16, void* out16, uint32_t stride,
+		             bool alone) const;
+		void backward_input(hipStream_t st, uint32_t B, const float* x, uint32_t x_stride, const void* params16, const void* dy16,
+		                    int dy_layout, uint32_t stride, float* dx) const;
 	};
 	std::vector<Part> parts;
-	std::string composite_otype;  // "Composite", or the single part's own otype when it stands alone
-	CompTable table{};            // the parts as the kernels read them (layout())
-	uint32_t n_comp_params = 0;
+	std::string otype;  // as spelled: "Composite", or the lone part's own ("Grid", "OneBlob", "SphericalHarmonics", ...)
+	CompTable table{};  // the parts as the composite kernels read them (encodings that run them only)
+	uint32_t n_grid_params = 0;
 
 	EncodingHost(uint32_t n_dims_to_encode, const json& enc);
 	static bool known(const std::string& otype);
-	uint32_t n_output_unpadded() const;
-	uint32_t padded_output_width() const {
-		return kind == EncKind::Grid ? grid->padded_output_width() : kind == EncKind::Composite ? table.width : n_output_unpadded() + n_to_pad;
-	}
-	void set_alignment(uint32_t a);
-	uint32_t n_params() const { return kind == EncKind::Grid ? grid->n_params : kind == EncKind::Composite ? n_comp_params : 0u; }
+	static bool is_grid_otype(const std::string& otype);
+	// the part that stands alone and runs its own kernel; nullptr: the composite kernels run
+	const Part* lone_part() const { return otype != "Composite" && parts[0].own_kernel() ? &parts[0] : nullptr; }
+	GridEncodingHost* lone_grid() const { return lone_part() ? parts[0].grid.get() : nullptr; }
+	uint32_t padded_output_width() const { return parts.empty() ? 0u : parts.back().out_col + parts.back().width; }
+	void set_alignment(uint32_t a) { layout(a); }  // Encoding::set_alignment (encoding.h)
+	uint32_t n_params() const { return n_grid_params; }
 	void initialize_params(Pcg32& rng, float* host_out, float scale = 1.0f) const;
 	json hyperparams() const;
 	// the reference's class name (SphericalHarmonicsEncoding, CompositeEncoding, ...)
-	std::string name() const;
+	std::string name() const { return otype + "Encoding"; }
 	// encoded output AoS fp16 [B][padded_output_width()] (padding: grid 0, OneBlob / Identity /
 	// TriangleWave 1 after the values, SphericalHarmonics 1 before them)
 	void forward_aos(hipStream_t st, uint32_t B, const float* x, const void* params16, void* out16) const;
-	// dL/dx fp32 [B][n_dims] from dL/d(encoding) fp16 AoS; params16 = the encoding's parameters (grid)
-	// dy16: AoS [B][padded width]; grid encodings also take dy_layout 0 (level-major pairs [L][B])
+	// The layout the backward reads dL/d(encoding) fp16 in (launch_grid_bwd): AoS [B][padded width]
+	// (2), or for a lone grid with feature pairs and no padding level-major pairs [L][B] (0), which
+	// its backward reads coalesced (AoS rows would cost one 64-byte line per 4-byte read)
+	int dy_layout() const {
+		const GridEncodingHost* g = lone_grid();
+		return g && g->desc.n_features_per_level == 2 && g->n_to_pad == 0 ? 0 : 2;
+	}
+	// dL/dx fp32 [B][n_dims]; params16 = the encoding's parameters (grids). dy_layout: 2, or what
+	// dy_layout() allows
 	void backward_input(hipStream_t st, uint32_t B, const float* x, const void* dy16, float* dx, const void* params16 = nullptr,
 	                    int dy_layout = 2) const;
-	// Composite: the fp32 gradient of every nested grid's table from dL/d(encoding) AoS fp16
-	// [B][padded width], into grad32 [n_params()] (each grid's slice in nested order)
-	void backward_params(hipStream_t st, uint32_t B, const float* x, const void* dy16, float* grad32) const;
+	// the fp32 gradient of every grid's table into grad32 [n_params()] (each grid's slice in order),
+	// each grid with its own scratch
+	void backward_params(hipStream_t st, uint32_t B, const float* x, const void* dy16, int dy_layout, float* grad32) const;
 
 private:
 	void parse_composite(const json& enc);
 	void add_part(uint32_t n_in, uint32_t in_col, const json& enc);
-	void layout(uint32_t alignment);  // widths, columns and the kernel table
+	void layout(uint32_t alignment);  // widths, columns, parameter offsets (+ build_table)
+	void build_table();               // the composite kernels' argument, within its COMP_MAX_* limits
 };
 
 // Workspace for one fwd/bwd over a batch of B (sizes grow only).
@@ -289,12 +310,14 @@ struct NetworkHost {
 	GradFinalize grad_fin{};
 	bool grad_fin_done = false;
 	std::unique_ptr<EncodingHost> enc;
-	GridEncodingHost* grid = nullptr;  // enc->grid when the encoding is a grid
+	GridEncodingHost* grid = nullptr;  // enc->lone_grid(), cached: the fused path reads it every step
 	MlpHost mlp;
 	uint32_t n_input_dims = 0, n_output_dims = 0;
 	uint32_t loss_l2 = 0;  // training loss: 0 RelativeL2 (relative_l2.h), 1 L2 (l2.h)
 	NetworkHost(uint32_t n_in, uint32_t n_out, const json& enc, const json& net);
 	uint64_t n_params() const { return (uint64_t)mlp.n_params() + enc->n_params(); }
+	// the encoding's parameters inside params16 ([mlp | encoding] fp16)
+	const void* enc_params(const void* params16) const { return (const uint8_t*)params16 + (size_t)mlp.n_params() * 2; }
 	bool fused_ok() const;   // register-resident kernel (mlp_fused.h): grid input, W <= 64
 	bool tile_shape_ok() const;  // tile kernels (mlp_tile.h): FullyFusedMLP W in {16..128}, any encoding, IN <= 128, H <= 5
 	bool tile_ok() const;        // the training engine is the tile kernel (tile_shape_ok and not fused_ok)

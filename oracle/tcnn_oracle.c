@@ -1126,13 +1126,15 @@ static int model_encode(const orc_model* m, uint32_t B, const float* pos, uint16
 		return 0;
 	}
 	orc_grid_fwd(&m->grid, B, pos, m->w16 + m->n_mlp_params, enc);
+	const uint32_t LF = m->grid.n_levels * m->grid.n_features_per_level;
+	memset(enc + (size_t)LF * B, 0, (size_t)(m->IN - LF) * B * 2); /* padding rows: 0 (grid.h set_padded_output_width) */
 	return 1;
 }
 
 int orc_model_init(orc_model* m, uint32_t seed) {
 	if (m->enc_type == 0) {
 		if (orc_grid_init(&m->grid) != 0) return -1;
-		m->IN = m->grid.n_levels * m->grid.n_features_per_level;
+		m->IN = (m->grid.n_levels * m->grid.n_features_per_level + 15) / 16 * 16; /* network alignment, network.cu:76-95 */
 	}
 	const uint32_t IN = m->IN;
 	m->n_mlp_params = orc_mlp_n_params(m->W, IN, m->NH, m->OUTP);

@@ -12,7 +12,8 @@ import numpy as np
 import pytest
 
 import test_composite_reference as R
-from helpers import GOLD, assert_within_fp16_ulps, assert_wgrad_per_element, rel_err, relu_margin_ok, trainer_arrays
+from helpers import (CONFIG_HASH, GOLD, assert_within_fp16_ulps, assert_wgrad_per_element, make_batch, rel_err, relu_margin_ok,
+                     trainer_arrays)
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -579,3 +580,118 @@ def test_trainer_snapshots(torch_mod):
         assert not np.array_equal(t2.inference(xd).cpu().numpy(), before)
         t2.deserialize(snap)
         np.testing.assert_array_equal(t2.inference(xd).cpu().numpy(), before)
+
+
+# ---------------------------------------------------------------------------------------------
+# 11: every encoding is a part list -- a lone encoding against its one-part Composite
+# ---------------------------------------------------------------------------------------------
+GRID2_L5 = {"otype": "HashGrid", "n_levels": 5, "n_features_per_level": 2, "log2_hashmap_size": 12, "base_resolution": 8,
+            "per_level_scale": 1.5}
+DENSE3_F4 = {"otype": "DenseGrid", "n_levels": 3, "n_features_per_level": 4, "base_resolution": 4, "per_level_scale": 2.0}
+LONE = [(2, {"otype": "OneBlob", "n_bins": 64}, 0, 128),
+        (3, {"otype": "OneBlob", "n_bins": 16}, 32, 64),
+        (3, {"otype": "Identity", "scale": 1.5, "offset": -0.25}, 16, 16),
+        (2, GRID2_L5, 0, 10),
+        (3, DENSE3_F4, 0, 12)]
+
+
+@pytest.mark.parametrize("n_in,enc,alignment,width", LONE, ids=["oneblob64", "oneblob16_padded", "identity_padded", "hashgrid", "densegrid"])
+def test_lone_encoding_equals_one_part_composite(torch_mod, n_in, enc, alignment, width):
+    """X alone runs its own kernel (encodings.hip, grid.hip), {"otype": "Composite", "nested": [X]} the
+    composite kernels: forward, dL/dinput and dL/dparams are bit-equal at B = 1000 (not a multiple of 64
+    or 256: the kernels' tails run). OneBlob and Identity evaluate the same fp32 operation sequence in
+    both; the grid kernels are the same, and the grid backward sums in integers in LDS."""
+    lone = Mod(torch_mod, n_in, enc, alignment=alignment)
+    comp = Mod(torch_mod, n_in, {"otype": "Composite", "nested": [enc]}, alignment=alignment)
+    assert lone.width == comp.width == width and lone.n_params == comp.n_params
+    rng = np.random.default_rng(17)
+    B = 1000
+    x = rng.uniform(0, 1, (B, n_in)).astype(np.float32)
+    table = O.f2h(rng.uniform(-1, 1, lone.n_params).astype(np.float32)) if lone.n_params else None
+    dy16 = O.f2h(rng.standard_normal((B, width)).astype(np.float32))
+    got = []
+    for m in (lone, comp):
+        out = m.forward(x, table)
+        dx, grad = m.backward(dy16)
+        assert not np.isnan(O.h2f(out)).any() and not np.isnan(dx).any()
+        got.append((out, dx, grad))
+        m.close()
+    np.testing.assert_array_equal(got[0][0], got[1][0])
+    np.testing.assert_array_equal(got[0][1].view(np.uint32), got[1][1].view(np.uint32))
+    if lone.n_params:
+        assert not np.isnan(got[0][2]).any() and np.abs(got[0][2]).max() > 0
+        np.testing.assert_array_equal(got[0][2].view(np.uint32), got[1][2].view(np.uint32))
+
+
+def test_lone_encodings_keep_no_table_limits(torch_mod):
+    """The composite kernels' table limits (64 input dims, 256 columns) do not bind a lone Identity or
+    OneBlob: 80 input dims, and 7 dims x 64 bins = 448 columns. Forward bit-equal to the oracle (Identity:
+    fp16(fma(x, scale, offset))), dL/dinput against the oracle (Identity: the reference's statement) to the
+    tolerance of test_gpu_layered.py's test_oneblob_encoding_bit_exact (rtol = atol = 1e-5)."""
+    rng = np.random.default_rng(23)
+    B = 300
+    x = rng.uniform(0, 1, (B, 80)).astype(np.float32)
+    m = Mod(torch_mod, 80, {"otype": "Identity", "scale": 0.75, "offset": 0.125})
+    assert m.width == 80
+    np.testing.assert_array_equal(m.forward(x), O.identity_fwd(x, 0.75, 0.125))
+    dy16 = O.f2h(rng.standard_normal((B, 80)).astype(np.float32))
+    dx, _ = m.backward(dy16)
+    # identity.h:84: dL/dx = (T)((float)dL/dy * scale), the fp32 product (exact: 11 x 2 significant bits) rounded to fp16
+    np.testing.assert_allclose(dx, O.h2f(O.f2h(0.75 * O.h2f(dy16))), rtol=1e-5, atol=1e-5)
+    m.close()
+
+    x = rng.uniform(0, 1, (B, 7)).astype(np.float32)
+    m = Mod(torch_mod, 7, {"otype": "OneBlob", "n_bins": 64})
+    assert m.width == 448
+    np.testing.assert_array_equal(m.forward(x), O.oneblob_fwd(x, 64))
+    dy16 = O.f2h(rng.standard_normal((B, 448)).astype(np.float32))
+    dx, _ = m.backward(dy16)
+    np.testing.assert_allclose(dx, O.oneblob_bwd(x, 64, dy16), rtol=1e-5, atol=1e-5)
+    m.close()
+
+
+def test_padded_lone_grid_through_network(torch_mod):
+    """A lone grid of 10 features under a W64/H2 network: the network's alignment 16 pads it with 6 zero
+    columns and the model trains on the tile engine. One loss-driven step at B = 512 against
+    oracle.OracleModel: the bounds of test_gpu_layered.py's test_layered_step_gradients_and_loss for
+    W64 grid configs (loss 1e-3 relative, gradient relative L2 <= 1e-3 for the network and for the grid)."""
+    from tinycudann import Trainer
+    cfg = dict(CONFIG_HASH, encoding=GRID2_L5,
+               network={"otype": "FullyFusedMLP", "activation": "ReLU", "output_activation": "None", "n_neurons": 64, "n_hidden_layers": 2})
+    t = Trainer(2, 3, cfg, seed=1337)
+    assert t.engine == "fused"
+    om = O.OracleModel(cfg, 2, 3, seed=1337)
+    nm = O.mlp_n_params(64, 16, 2, 16)
+    assert t.n_params == om.n_params == nm + O.grid_cfg(GRID2_L5, 2).n_params and om.n_mlp_params == nm
+    np.testing.assert_array_equal(trainer_arrays(t)["w16"], om.w16)
+    pos, tgt = make_batch(512)
+    t.training_step(torch_mod.from_numpy(pos).cuda(), torch_mod.from_numpy(tgt).cuda(), run_optimizer=False)
+    loss, loss_ref = t.loss(), om.train_step(pos, tgt, run_optimizer=False, n_threads=4)
+    assert abs(loss - loss_ref) <= 1e-3 * abs(loss_ref), (loss, loss_ref)
+    g32 = trainer_arrays(t)["g32"]
+    e_mlp, e_grid = rel_err(g32[:nm], om.grad32[:nm]), rel_err(g32[nm:], om.grad32[nm:])
+    print("padded lone grid gradient relative L2: mlp", e_mlp, "grid", e_grid)
+    assert e_mlp <= 1e-3, e_mlp
+    assert e_grid <= 1e-3, e_grid
+
+
+def test_encoding_module_names_and_hyperparams(torch_mod):
+    """name() and hyperparams() of the six spellings (no kernel runs), and the alignment a lone grid refuses"""
+    from tinycudann import _lib as L
+    lib = L.lib()
+    grid_hyper = {"otype": "Grid", "type": "Hash", "n_levels": 5, "n_features_per_level": 2, "base_resolution": 8, "per_level_scale": 1.5,
+                  "interpolation": "Linear", "hash": "CoherentPrime", "log2_hashmap_size": 12}
+    blob = {"otype": "OneBlob", "n_bins": 4}
+    cases = [(2, GRID2_L5, "GridEncoding", grid_hyper),
+             (2, blob, "OneBlobEncoding", blob),
+             (3, {"otype": "Identity", "scale": 1.5, "offset": -0.25}, "IdentityEncoding", {"otype": "Identity", "scale": 1.5, "offset": -0.25}),
+             (3, {"otype": "SphericalHarmonics", "degree": 3}, "SphericalHarmonicsEncoding", {"otype": "SphericalHarmonics", "degree": 3}),
+             (2, {"otype": "TriangleWave", "n_frequencies": 5}, "TriangleWaveEncoding", {"otype": "TriangleWave", "n_frequencies": 5}),
+             (2, {"otype": "Composite", "nested": [blob]}, "CompositeEncoding", {"otype": "Composite", "nested": [blob]})]
+    for n_in, enc, name, hyper in cases:
+        m = Mod(torch_mod, n_in, enc)
+        assert lib.tcnn_module_name(m.h).decode() == name
+        assert json.loads(lib.tcnn_module_hyperparams(m.h).decode()) == hyper
+        m.close()
+    assert not lib.tcnn_create_encoding_aligned(2, json.dumps(GRID2_L5).encode(), 1, 16)
+    assert lib.tcnn_last_error().decode() == "create_encoding: a grid encoding module takes no alignment"
