@@ -16,8 +16,10 @@
  *                         object.h:147-179) used by mlp_learning_an_image.
  *
  * Matrix conventions (reference common.h:157-167): input fp32 [n x n_input_dims] row-major
- * (= CM [n_input_dims x n]); outputs / params are fp16 when precision is Fp16; n must be a multiple
- * of tcnn_batch_size_granularity() (256).
+ * (= CM [n_input_dims x n]); outputs / params / dL_doutput / dL_dparams / dL_ddLdoutput have the module's
+ * precision (tcnn_module_param_precision / _output_precision): fp16 for every network module, fp16 or
+ * fp32 for an encoding module as it was created; n must be a multiple of tcnn_batch_size_granularity()
+ * (256) for networks (encoding modules take any n).
  */
 #ifndef TCNN_MI355X_H
 #define TCNN_MI355X_H
@@ -67,7 +69,10 @@ tcnn_module* tcnn_create_network_with_input_encoding(uint32_t n_input_dims, uint
                                                      const char* encoding_json, const char* network_json);
 /* cpp::create_network(n_input_dims, n_output_dims, network) (= Identity encoding + network) */
 tcnn_module* tcnn_create_network(uint32_t n_input_dims, uint32_t n_output_dims, const char* network_json);
-/* cpp::create_encoding(n_input_dims, encoding, requested_precision) */
+/* cpp::create_encoding(n_input_dims, encoding, requested_precision): TCNN_PRECISION_FP16, or
+   TCNN_PRECISION_FP32 for a module whose parameters, output rows, dL_doutput and dL_dparams are fp32 with
+   fp32 arithmetic in between (nothing narrowed to fp16; create_encoding<float>, Encoding(dtype=float32)).
+   Layout, widths, parameter order, initial parameters, hyperparams and name do not depend on it. */
 tcnn_module* tcnn_create_encoding(uint32_t n_input_dims, const char* encoding_json, int precision);
 /* create_encoding<T>(n_dims_to_encode, encoding, alignment): the encoded width padded to a multiple of
    `alignment` (0: no padding). Not for a grid encoding standing alone. */
@@ -89,7 +94,9 @@ int tcnn_module_backward(tcnn_module* m, void* stream, const tcnn_context* ctx, 
  * rounded to fp16, the module's backward runs on it, dL_dinput (fp32) is divided by loss_scale and
  * dL_dparams = fp16(fp16 gradient / loss_scale) -- stored as fp16, or widened to fp32 when
  * dparams_fp32 (the gradient of fp32 master parameters cast to fp16 for the module) -- the same
- * values the binding computes with three torch operations. */
+ * values the binding computes with three torch operations. An Fp32 encoding module does the same three
+ * steps in fp32 (dL_doutput * loss_scale, backward, both gradients divided by loss_scale); its dL_dparams
+ * is fp32 whatever dparams_fp32 says. */
 int tcnn_module_backward_scaled(tcnn_module* m, void* stream, const tcnn_context* ctx, uint32_t n, float* dL_dinput,
                                 const void* dL_doutput, void* dL_dparams, const float* input, const void* output,
                                 const void* params, float loss_scale, int dparams_fp32);
@@ -116,6 +123,7 @@ int tcnn_module_set_max_level_gpu(tcnn_module* m, const float* max_level_per_poi
 uint32_t tcnn_module_n_input_dims(const tcnn_module* m);
 uint32_t tcnn_module_n_output_dims(const tcnn_module* m); /* padded width (cpp_api.cu:130) */
 uint64_t tcnn_module_n_params(const tcnn_module* m);
+/* the module's own precision (TCNN_PRECISION_*): Fp32 for an encoding created with it, else Fp16 */
 int tcnn_module_param_precision(const tcnn_module* m);
 int tcnn_module_output_precision(const tcnn_module* m);
 /* Module::initialize_params(seed, params_full_precision, scale): pcg32{seed} (cpp_api.cu:133-136);

@@ -5,7 +5,12 @@
 // tcnn::cpp::Module in cpp_api.h). The Trainer of this engine trains a network behind an encoding:
 // a Trainer constructed over an Encoding alone refuses it (engine_network() is null) rather than
 // training something else.
+// T is the module's precision: Encoding<__half> holds fp16 parameters and runs the fp16 kernels,
+// Encoding<float> / create_encoding<float> creates an Fp32 module (fp32 parameters, fp32 output, nothing
+// narrowed to fp16 in between).
 #pragma once
+
+#include <type_traits>
 
 #include "object.h"
 
@@ -15,21 +20,26 @@ template <typename T>
 class Encoding : public DifferentiableObject<float, T, T> {
 public:
 	Encoding(uint32_t n_dims_to_encode, const json& encoding, uint32_t seed = 1337) : m_n_dims{n_dims_to_encode}, m_encoding(encoding) {
-		m_module = detail::check_handle(tcnn_create_encoding(n_dims_to_encode, encoding.dump().c_str(), TCNN_PRECISION_FP16));
+		m_module = detail::check_handle(tcnn_create_encoding(n_dims_to_encode, encoding.dump().c_str(), F32 ? TCNN_PRECISION_FP32 : TCNN_PRECISION_FP16));
 		// its own parameters (the grid table; none for OneBlob / Identity), initialised as the
-		// reference's encodings initialise theirs (grid.h: uniform in +-1e-4), stored fp16
+		// reference's encodings initialise theirs (grid.h: uniform in +-1e-4), stored at precision T
 		const size_t n = n_params();
 		if (n) {
-			GPUMemory<float> p32(n);
-			detail::check_rc(tcnn_module_initialize_params(m_module, seed, p32.data(), 1.0f));
 			m_params.resize(n);
-			hipLaunchKernelGGL(detail::narrow_from_float<__half>, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, nullptr, (uint32_t)n, p32.data(),
-			                   m_params.data());
+			if constexpr (F32) {
+				detail::check_rc(tcnn_module_initialize_params(m_module, seed, m_params.data(), 1.0f));
+			} else {
+				GPUMemory<float> p32(n);
+				detail::check_rc(tcnn_module_initialize_params(m_module, seed, p32.data(), 1.0f));
+				hipLaunchKernelGGL(detail::narrow_from_float<__half>, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, nullptr, (uint32_t)n, p32.data(),
+				                   m_params.data());
+			}
 			HIP_CHECK_THROW(hipDeviceSynchronize());
 		}
 	}
-	// the parameters inference runs on (fp16, n_params(); the module's precision)
-	__half* params() const { return m_params.data(); }
+	// the parameters inference runs on (n_params() of T, the module's precision)
+	T* params() const { return m_params.data(); }
+	int param_precision() const { return tcnn_module_param_precision(m_module); }
 	~Encoding() override { tcnn_module_destroy(m_module); }
 	Encoding(const Encoding&) = delete;
 	Encoding& operator=(const Encoding&) = delete;
@@ -46,9 +56,13 @@ public:
 
 protected:
 	// object.h inference without a Trainer: the module's forward on this encoding's own parameters,
-	// fp16 output widened into the fp32 matrix
+	// fp16 output widened into the fp32 matrix (an fp32 module writes the matrix itself)
 	bool inference_standalone(hipStream_t stream, const GPUMatrixDynamic<float>& input, GPUMatrixDynamic<float>& output) override {
 		const uint32_t n = input.n(), w = padded_output_width();
+		if constexpr (F32) {
+			detail::check_rc(tcnn_module_inference(m_module, stream, n, input.data(), output.data(), m_params.data()));
+			return true;
+		}
 		m_out16.enlarge((size_t)n * w);
 		detail::check_rc(tcnn_module_inference(m_module, stream, n, input.data(), m_out16.data(), m_params.data()));
 		const uint32_t ne = n * w;
@@ -57,10 +71,11 @@ protected:
 	}
 
 private:
+	static constexpr bool F32 = std::is_same<T, float>::value;
 	uint32_t m_n_dims;
 	json m_encoding;
 	tcnn_module* m_module = nullptr;
-	GPUMemory<__half> m_params;
+	GPUMemory<T> m_params;
 	GPUMemory<__half> m_out16;
 };
 

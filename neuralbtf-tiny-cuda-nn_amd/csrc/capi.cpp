@@ -103,6 +103,10 @@ struct ModuleBase {
 		throw std::runtime_error("DifferentiableObject::backward_backward_input_impl: not implemented error");
 	}
 	virtual GridEncodingHost* grid_encoding() { return nullptr; }
+	// precision of the parameters, the output, dL/doutput and dL/dparams (TCNN_PRECISION_*): fp16 for
+	// every module but an encoding created with Fp32
+	virtual int precision() const { return TCNN_PRECISION_FP16; }
+	size_t elem_bytes() const { return precision() == TCNN_PRECISION_FP32 ? 4 : 2; }
 	virtual const char* engine() const { return "encoding"; }
 	virtual const char* inference_engine() const { return "encoding"; }
 	virtual uint32_t n_input_dims() const = 0;
@@ -216,9 +220,10 @@ struct ModuleNWIE : ModuleBase {
 struct ModuleEncoding : ModuleBase {
 	EncodingHost enc;
 	DevBuf grad32;
-	ModuleEncoding(uint32_t n_in, const json& j, uint32_t alignment) : enc(n_in, j) {
+	ModuleEncoding(uint32_t n_in, const json& j, uint32_t alignment, bool f32) : enc(n_in, j, f32) {
 		if (alignment > 0) enc.set_alignment(alignment);
 	}
+	int precision() const override { return enc.f32 ? TCNN_PRECISION_FP32 : TCNN_PRECISION_FP16; }
 	void inference(hipStream_t st, uint32_t n, const float* in, void* out, const void* params) override {
 		enc.forward_aos(st, n, in, params, out);
 	}
@@ -230,6 +235,7 @@ struct ModuleEncoding : ModuleBase {
 	              const void*, const void* params) override {
 		if (dL_din) enc.backward_input(st, n, in, dL_dout, dL_din, params);
 		if (!dL_dparams || !enc.n_params()) return;
+		if (enc.f32) return enc.backward_params(st, n, in, dL_dout, 2, (float*)dL_dparams);  // fp32 dL/dparams: the sums themselves
 		grad32.reserve((size_t)enc.n_params() * 4);
 		enc.backward_params(st, n, in, dL_dout, 2, grad32.as<float>());
 		launch_cast_f32_f16(st, grad32.as<float>(), dL_dparams, enc.n_params());
@@ -241,11 +247,16 @@ struct ModuleEncoding : ModuleBase {
 		if (!grid) return ModuleBase::backward_backward_input(st, n, dL_ddLdin, in, dL_dout, dL_dparams, dL_ddLdout, dL_din, params);
 		if (!dL_ddLdout && !dL_dparams) return;  // grid.h:913-915
 		TCNN_CHECK(params, "backward_backward_input needs the grid parameters");
+		const uint32_t W = enc.padded_output_width();
+		if (enc.f32) {  // fp32 module: the fp32 atomics accumulate straight into dL/dparams
+			if (dL_dparams) TCNN_HIP_CHECK(hipMemsetAsync(dL_dparams, 0, (size_t)grid->n_params * 4, st));  // GradientMode::Overwrite
+			return grid->backward_backward_input_f32(st, n, in, enc.n_dims, (const float*)params, dL_ddLdin, (const float*)dL_dout, W,
+			                                         (float*)dL_dparams, (float*)dL_ddLdout, W, dL_din);
+		}
 		if (dL_dparams) {
 			grad32.reserve((size_t)grid->n_params * 4);
 			TCNN_HIP_CHECK(hipMemsetAsync(grad32.p, 0, (size_t)grid->n_params * 4, st));  // GradientMode::Overwrite
 		}
-		const uint32_t W = enc.padded_output_width();
 		grid->backward_backward_input(st, n, in, enc.n_dims, params, dL_ddLdin, dL_dout, W, dL_dparams ? grad32.as<float>() : nullptr,
 		                              dL_ddLdout, W, dL_din);
 		if (dL_dparams) launch_cast_f32_f16(st, grad32.as<float>(), dL_dparams, grid->n_params);
@@ -358,13 +369,13 @@ tcnn_module* tcnn_create_network(uint32_t n_in, uint32_t n_out, const char* net)
 // standing alone takes no alignment here.
 tcnn_module* tcnn_create_encoding_aligned(uint32_t n_in, const char* enc, int precision, uint32_t alignment) {
 	return guard_ptr<tcnn_module>([&] {
-		TCNN_CHECK(precision == TCNN_PRECISION_FP16, "create_encoding: only Fp16 precision is implemented by the MI355X engine");
+		TCNN_CHECK(precision == TCNN_PRECISION_FP16 || precision == TCNN_PRECISION_FP32, "create_encoding: precision must be Fp16 or Fp32");
 		json j = parse_json(enc);
 		const std::string ot = j.is_object() && j.find("otype") != j.end() ? j["otype"].get<std::string>() : "OneBlob";
 		TCNN_CHECK(EncodingHost::known(ot), "Encoding '" + ot + "' is not implemented by the MI355X engine yet");
 		TCNN_CHECK(alignment == 0 || !EncodingHost::is_grid_otype(ot), "create_encoding: a grid encoding module takes no alignment");
 		auto r = std::make_unique<tcnn_module>();
-		r->m = std::make_unique<ModuleEncoding>(n_in, j, alignment);
+		r->m = std::make_unique<ModuleEncoding>(n_in, j, alignment, precision == TCNN_PRECISION_FP32);
 		return r.release();
 	});
 }
@@ -394,7 +405,7 @@ int tcnn_module_backward(tcnn_module* m, void* stream, const tcnn_context* ctx, 
 	return guard([&] {
 		TCNN_CHECK(ctx != nullptr, "backward: null context");
 		if (n == 0) {  // empty batch: Overwrite-mode gradients are all zero
-			if (dL_dparams) TCNN_HIP_CHECK(hipMemsetAsync(dL_dparams, 0, m->m->n_params() * 2, (hipStream_t)stream));
+			if (dL_dparams) TCNN_HIP_CHECK(hipMemsetAsync(dL_dparams, 0, m->m->n_params() * m->m->elem_bytes(), (hipStream_t)stream));
 			return;
 		}
 		TCNN_CHECK(ctx->n == n, "backward: batch size differs from the forward's");
@@ -410,14 +421,23 @@ int tcnn_module_backward_scaled(tcnn_module* m, void* stream, const tcnn_context
 		TCNN_CHECK(loss_scale != 0.0f, "backward: loss scale must be nonzero");
 		const hipStream_t st = (hipStream_t)stream;
 		const uint64_t np = m->m->n_params();
+		const bool f32 = m->m->precision() == TCNN_PRECISION_FP32;  // fp32 module: dL/dparams is fp32 whatever dparams_fp32 says
 		if (n == 0) {
-			if (dL_dparams) TCNN_HIP_CHECK(hipMemsetAsync(dL_dparams, 0, np * (dparams_fp32 ? 4 : 2), st));
+			if (dL_dparams) TCNN_HIP_CHECK(hipMemsetAsync(dL_dparams, 0, np * ((dparams_fp32 || f32) ? 4 : 2), st));
 			return;
 		}
 		TCNN_CHECK(ctx->n == n, "backward: batch size differs from the forward's");
 		if (m->m->backward_scaled(st, ctx->impl.get(), n, dL_din, dL_dout, dL_dparams, in, out, params, loss_scale, dparams_fp32 != 0))
 			return;
 		const size_t n_out = (size_t)n * m->m->n_output_dims();
+		if (f32) {  // the same three steps in fp32: dL/dy * s, backward, dL/dinput and dL/dparams divided by s
+			m->dout_scaled.reserve(n_out * 4);
+			launch_scale_f32(st, (const float*)dL_dout, m->dout_scaled.as<float>(), loss_scale, n_out);
+			m->m->backward(st, ctx->impl.get(), n, dL_din, m->dout_scaled.p, dL_dparams, in, out, params);
+			if (dL_din) launch_div_f32(st, dL_din, loss_scale, (size_t)n * m->m->n_input_dims());
+			if (dL_dparams) launch_div_f32(st, (float*)dL_dparams, loss_scale, np);
+			return;
+		}
 		m->dout_scaled.reserve(n_out * 2);
 		launch_scale_f16(st, dL_dout, m->dout_scaled.p, loss_scale, n_out);  // modules.py:135 doutput * loss_scale
 		void* g16 = dL_dparams;
@@ -437,7 +457,7 @@ int tcnn_module_backward_backward_input(tcnn_module* m, void* stream, const tcnn
 	return guard([&] {
 		TCNN_CHECK(ctx != nullptr, "backward_backward_input: null context");
 		if (n == 0) {
-			if (dL_dparams) TCNN_HIP_CHECK(hipMemsetAsync(dL_dparams, 0, m->m->n_params() * 2, (hipStream_t)stream));
+			if (dL_dparams) TCNN_HIP_CHECK(hipMemsetAsync(dL_dparams, 0, m->m->n_params() * m->m->elem_bytes(), (hipStream_t)stream));
 			return;
 		}
 		m->m->backward_backward_input((hipStream_t)stream, n, dL_ddLdin, in, dL_dout, dL_dparams, dL_ddLdout, dL_din, params);
@@ -465,8 +485,8 @@ int tcnn_module_set_max_level_gpu(tcnn_module* m, const float* max_level_per_poi
 uint32_t tcnn_module_n_input_dims(const tcnn_module* m) { return m->m->n_input_dims(); }
 uint32_t tcnn_module_n_output_dims(const tcnn_module* m) { return m->m->n_output_dims(); }
 uint64_t tcnn_module_n_params(const tcnn_module* m) { return m->m->n_params(); }
-int tcnn_module_param_precision(const tcnn_module*) { return TCNN_PRECISION_FP16; }
-int tcnn_module_output_precision(const tcnn_module*) { return TCNN_PRECISION_FP16; }
+int tcnn_module_param_precision(const tcnn_module* m) { return m->m->precision(); }
+int tcnn_module_output_precision(const tcnn_module* m) { return m->m->precision(); }
 int tcnn_module_initialize_params(tcnn_module* m, uint64_t seed, float* p, float scale) {
 	return guard([&] { m->m->initialize_params(seed, p, scale); });
 }

@@ -43,13 +43,20 @@ __device__ __forceinline__ float wrapped_cdf(float boundary, float x, float n_bi
 	return c + lo + hi;
 }
 
-// All n_bins OneBlob outputs of one input value, handed to put(bin, fp16 value).
+// An encoded fp32 value at the module's precision T: rounded once to fp16, or kept (fp32 modules).
+template <typename T>
+__device__ __forceinline__ T enc_value(float v) {
+	if constexpr (sizeof(T) == 2) return f16_rn(v);
+	else return v;
+}
+
+// All n_bins OneBlob outputs of one input value, handed to put(bin, value at precision T).
 // The reference evaluates each bin's left CDF in its own lane and takes the right CDF from lane
 // (bin + 1) with __shfl_sync(..., bin + 1, n_bins) (oneblob.h:53-62). On its 32-lane warps a shuffle
 // width above 32 acts as width 32, so for n_bins > 32 the source lane wraps inside each 32-bin
 // group: bin b reads the left CDF of bin (b & ~31) + ((b + 1) & 31), and only the last bin of the
 // dimension adds the wrap-around 1. This reproduces exactly that (S = min(n_bins, 32)).
-template <typename Put>
+template <typename T = _Float16, typename Put>
 __device__ __forceinline__ void oneblob_fwd_dim(float xv, uint32_t n_bins, uint32_t log2_bins, Put&& put) {
 	const float nb = (float)n_bins;
 	const uint32_t S = n_bins < 32 ? n_bins : 32;
@@ -61,14 +68,15 @@ __device__ __forceinline__ void oneblob_fwd_dim(float xv, uint32_t n_bins, uint3
 			float right;
 			if (j + 1 < S) right = wrapped_cdf(scalbnf((float)(b + 1), -(int)log2_bins), xv, nb);
 			else right = first + (b == n_bins - 1 ? 1.0f : 0.0f);
-			put(b, f16_rn(right - left));
+			put(b, enc_value<T>(right - left));
 			left = right;
 		}
 	}
 }
 
 // kernel_one_blob_backward (oneblob.h:116-147): dL/dx = sum_k dL/dy[k] * (D_left - D_right).
-__device__ __forceinline__ float oneblob_bwd_dim(float xv, uint32_t n_bins, uint32_t log2_bins, const _Float16* __restrict__ dy) {
+template <typename T>
+__device__ __forceinline__ float oneblob_bwd_dim(float xv, uint32_t n_bins, uint32_t log2_bins, const T* __restrict__ dy) {
 	const float nb = (float)n_bins;
 	float left = quartic_cdf_deriv(-xv, nb) + quartic_cdf_deriv(-xv - 1.0f, nb) + quartic_cdf_deriv(-xv + 1.0f, nb);
 	float result = 0.0f;
@@ -88,6 +96,9 @@ __device__ __forceinline__ _Float16 identity_fwd_value(float xv, float scale, fl
 }
 // identity_backward (identity.h:68-85): dL/dx = (T)(dL/dy * scale) -- stored as fp32
 __device__ __forceinline__ float identity_bwd_value(_Float16 dy, float scale) { return (float)f16_rn((float)dy * scale); }
+// the same with T = float (fp32 modules): no narrowing on either side
+__device__ __forceinline__ float identity_fwd_value_f32(float xv, float scale, float offset) { return __builtin_fmaf(xv, scale, offset); }
+__device__ __forceinline__ float identity_bwd_value(float dy, float scale) { return dy * scale; }
 
 // TriangleWave (triangle_wave.h:46-81), frequency k of one input value: v = x 2^(k-1) + k/4,
 // y = |v - floor(v) - 1/2| 4 - 1. Every operation is one correctly rounded fp32 operation (the

@@ -315,9 +315,29 @@ void launch_grid_fwd(hipStream_t st, uint32_t D, uint32_t F, HashType h, uint32_
 // kernel_grid_backward_input, grid.h:322-349), fused: dy_dx is recomputed per point from the table
 // instead of being stored by the forward ([L*F][B][D] fp32 = 256 B/sample of HBM traffic saved).
 // Same operation order and FMA contraction points as the reference (see the oracle).
-template <uint32_t D, uint32_t F, HashType H>
+// T = the module's precision (_Float16, or float for an fp32 encoding module): the type of the table
+// and of dL/dy; the arithmetic is fp32 in both. fp32 dL/dy comes as AoS rows only.
+template <uint32_t F>
+__device__ __forceinline__ void load_dy_t(int layout, const _Float16* __restrict__ dLdy, uint32_t dy_stride, uint32_t level, uint32_t B,
+                                          uint32_t i, float* dy) {
+	load_dy<F>(layout, dLdy, dy_stride, level, B, i, dy);
+}
+template <uint32_t F>
+__device__ __forceinline__ void load_dy_t(int, const float* __restrict__ dLdy, uint32_t dy_stride, uint32_t level, uint32_t, uint32_t i,
+                                          float* dy) {
+#pragma unroll
+	for (uint32_t f = 0; f < F; ++f) dy[f] = dLdy[(size_t)i * dy_stride + level * F + f];
+}
+// an fp32 result stored at the module's precision: rounded once to fp16, or kept
+template <typename T>
+__device__ __forceinline__ T enc_round(float v) {
+	if constexpr (sizeof(T) == 2) return f16_rn(v);
+	else return v;
+}
+
+template <uint32_t D, uint32_t F, HashType H, typename T>
 __global__ __launch_bounds__(256) void k_grid_bwd_input(uint32_t B, uint32_t L, const float* __restrict__ pos, uint32_t pstride,
-                                                        const _Float16* __restrict__ table, const _Float16* __restrict__ dLdy,
+                                                        const T* __restrict__ table, const T* __restrict__ dLdy,
                                                         int layout, uint32_t dy_stride, float* __restrict__ dx, uint32_t dx_stride,
                                                         const LevelInfo* __restrict__ levels, uint32_t hash_grid, uint32_t interp_u,
                                                         const GridOpts o) {
@@ -358,7 +378,10 @@ __global__ __launch_bounds__(256) void k_grid_bwd_input(uint32_t B, uint32_t L, 
 		if (interp != Interp::Nearest) {
 #pragma unroll
 			for (uint32_t gd = 0; gd < D; ++gd) {
-#pragma unroll
+				// fp32 tables of wide levels (D = 4, F = 8: 64 gathers of 32 bytes per level when every edge is
+				// unrolled) are walked one edge at a time, or the hoisted loads spill
+				constexpr uint32_t EDGE_UNROLL = (sizeof(T) == 4 && D * F >= 32) ? 1u : (1u << (D - 1));
+#pragma unroll EDGE_UNROLL
 				for (uint32_t idx = 0; idx < (1u << (D - 1)); ++idx) {
 					float w = li.scale;
 					uint32_t local[D];
@@ -381,7 +404,7 @@ __global__ __launch_bounds__(256) void k_grid_bwd_input(uint32_t B, uint32_t L, 
 			}
 		}
 		float dy[F];
-		load_dy<F>(layout, dLdy, dy_stride, l, B, i, dy);
+		load_dy_t<F>(layout, dLdy, dy_stride, l, B, i, dy);
 #pragma unroll
 		for (uint32_t f = 0; f < F; ++f)
 #pragma unroll
@@ -391,44 +414,56 @@ __global__ __launch_bounds__(256) void k_grid_bwd_input(uint32_t B, uint32_t L, 
 	for (uint32_t d = 0; d < D; ++d) dx[(size_t)i * dx_stride + d] = res[d];
 }
 
-template <uint32_t D, uint32_t F>
-static void grid_bwd_input_h(hipStream_t st, HashType h, dim3 g, uint32_t B, uint32_t L, const float* pos, uint32_t ps, const _Float16* t,
-                             const _Float16* dy, int layout, uint32_t dys, float* dx, uint32_t dxs, const LevelInfo* lv, uint32_t hg,
+template <uint32_t D, uint32_t F, typename T>
+static void grid_bwd_input_h(hipStream_t st, HashType h, dim3 g, uint32_t B, uint32_t L, const float* pos, uint32_t ps, const T* t,
+                             const T* dy, int layout, uint32_t dys, float* dx, uint32_t dxs, const LevelInfo* lv, uint32_t hg,
                              uint32_t in, const GridOpts& go) {
 	switch (h) {
-		case HashType::Prime: hipLaunchKernelGGL((k_grid_bwd_input<D, F, HashType::Prime>), g, dim3(256), 0, st, B, L, pos, ps, t, dy, layout, dys, dx, dxs, lv, hg, in, go); break;
-		case HashType::ReversedPrime: hipLaunchKernelGGL((k_grid_bwd_input<D, F, HashType::ReversedPrime>), g, dim3(256), 0, st, B, L, pos, ps, t, dy, layout, dys, dx, dxs, lv, hg, in, go); break;
-		default: hipLaunchKernelGGL((k_grid_bwd_input<D, F, HashType::CoherentPrime>), g, dim3(256), 0, st, B, L, pos, ps, t, dy, layout, dys, dx, dxs, lv, hg, in, go); break;
+		case HashType::Prime: hipLaunchKernelGGL((k_grid_bwd_input<D, F, HashType::Prime, T>), g, dim3(256), 0, st, B, L, pos, ps, t, dy, layout, dys, dx, dxs, lv, hg, in, go); break;
+		case HashType::ReversedPrime: hipLaunchKernelGGL((k_grid_bwd_input<D, F, HashType::ReversedPrime, T>), g, dim3(256), 0, st, B, L, pos, ps, t, dy, layout, dys, dx, dxs, lv, hg, in, go); break;
+		default: hipLaunchKernelGGL((k_grid_bwd_input<D, F, HashType::CoherentPrime, T>), g, dim3(256), 0, st, B, L, pos, ps, t, dy, layout, dys, dx, dxs, lv, hg, in, go); break;
 	}
 }
 
-template <uint32_t D>
+template <uint32_t D, typename T>
 static void grid_bwd_input_f(hipStream_t st, uint32_t F, HashType h, dim3 g, uint32_t B, uint32_t L, const float* pos, uint32_t ps,
-                             const _Float16* t, const _Float16* dy, int layout, uint32_t dys, float* dx, uint32_t dxs,
+                             const T* t, const T* dy, int layout, uint32_t dys, float* dx, uint32_t dxs,
                              const LevelInfo* lv, uint32_t hg, uint32_t in, const GridOpts& go) {
 	switch (F) {
-		case 1: grid_bwd_input_h<D, 1>(st, h, g, B, L, pos, ps, t, dy, layout, dys, dx, dxs, lv, hg, in, go); break;
-		case 2: grid_bwd_input_h<D, 2>(st, h, g, B, L, pos, ps, t, dy, layout, dys, dx, dxs, lv, hg, in, go); break;
-		case 4: grid_bwd_input_h<D, 4>(st, h, g, B, L, pos, ps, t, dy, layout, dys, dx, dxs, lv, hg, in, go); break;
-		case 8: grid_bwd_input_h<D, 8>(st, h, g, B, L, pos, ps, t, dy, layout, dys, dx, dxs, lv, hg, in, go); break;
+		case 1: grid_bwd_input_h<D, 1, T>(st, h, g, B, L, pos, ps, t, dy, layout, dys, dx, dxs, lv, hg, in, go); break;
+		case 2: grid_bwd_input_h<D, 2, T>(st, h, g, B, L, pos, ps, t, dy, layout, dys, dx, dxs, lv, hg, in, go); break;
+		case 4: grid_bwd_input_h<D, 4, T>(st, h, g, B, L, pos, ps, t, dy, layout, dys, dx, dxs, lv, hg, in, go); break;
+		case 8: grid_bwd_input_h<D, 8, T>(st, h, g, B, L, pos, ps, t, dy, layout, dys, dx, dxs, lv, hg, in, go); break;
 		default: throw std::runtime_error("GridEncoding: n_features_per_level must be 1, 2, 4 or 8");
 	}
+}
+
+template <typename T>
+static void grid_bwd_input_t(hipStream_t st, uint32_t D, uint32_t F, HashType h, uint32_t B, uint32_t L, const float* pos, uint32_t pos_stride,
+                             const T* t, const T* dy, int dy_layout, uint32_t dy_stride, float* dx, uint32_t dx_stride,
+                             const LevelInfo* levels, bool hash_grid, Interp interp, const GridOpts& go) {
+	if (B == 0) return;
+	const dim3 g(div_round_up(B, 256));
+	switch (D) {
+		case 2: grid_bwd_input_f<2, T>(st, F, h, g, B, L, pos, pos_stride, t, dy, dy_layout, dy_stride, dx, dx_stride, levels, hash_grid, (uint32_t)interp, go); break;
+		case 3: grid_bwd_input_f<3, T>(st, F, h, g, B, L, pos, pos_stride, t, dy, dy_layout, dy_stride, dx, dx_stride, levels, hash_grid, (uint32_t)interp, go); break;
+		case 4: grid_bwd_input_f<4, T>(st, F, h, g, B, L, pos, pos_stride, t, dy, dy_layout, dy_stride, dx, dx_stride, levels, hash_grid, (uint32_t)interp, go); break;
+		default: throw std::runtime_error("GridEncoding: number of input dims must be 2, 3 or 4");
+	}
+	TCNN_HIP_CHECK(hipGetLastError());
 }
 
 void launch_grid_bwd_input(hipStream_t st, uint32_t D, uint32_t F, HashType h, uint32_t B, uint32_t L, const float* pos,
                            uint32_t pos_stride, const void* table16, const void* dLdy16, int dy_layout, uint32_t dy_stride, float* dx,
                            uint32_t dx_stride, const LevelInfo* levels, bool hash_grid, Interp interp, const GridOpts& go) {
-	if (B == 0) return;
-	const dim3 g(div_round_up(B, 256));
-	const _Float16* t = (const _Float16*)table16;
-	const _Float16* dy = (const _Float16*)dLdy16;
-	switch (D) {
-		case 2: grid_bwd_input_f<2>(st, F, h, g, B, L, pos, pos_stride, t, dy, dy_layout, dy_stride, dx, dx_stride, levels, hash_grid, (uint32_t)interp, go); break;
-		case 3: grid_bwd_input_f<3>(st, F, h, g, B, L, pos, pos_stride, t, dy, dy_layout, dy_stride, dx, dx_stride, levels, hash_grid, (uint32_t)interp, go); break;
-		case 4: grid_bwd_input_f<4>(st, F, h, g, B, L, pos, pos_stride, t, dy, dy_layout, dy_stride, dx, dx_stride, levels, hash_grid, (uint32_t)interp, go); break;
-		default: throw std::runtime_error("GridEncoding: number of input dims must be 2, 3 or 4");
-	}
-	TCNN_HIP_CHECK(hipGetLastError());
+	grid_bwd_input_t<_Float16>(st, D, F, h, B, L, pos, pos_stride, (const _Float16*)table16, (const _Float16*)dLdy16, dy_layout, dy_stride, dx,
+	                           dx_stride, levels, hash_grid, interp, go);
+}
+
+void launch_grid_bwd_input_f32(hipStream_t st, uint32_t D, uint32_t F, HashType h, uint32_t B, uint32_t L, const float* pos,
+                               uint32_t pos_stride, const float* table32, const float* dLdy32, uint32_t dy_stride, float* dx,
+                               uint32_t dx_stride, const LevelInfo* levels, bool hash_grid, Interp interp, const GridOpts& go) {
+	grid_bwd_input_t<float>(st, D, F, h, B, L, pos, pos_stride, table32, dLdy32, 2, dy_stride, dx, dx_stride, levels, hash_grid, interp, go);
 }
 
 
@@ -439,14 +474,14 @@ void launch_grid_bwd_input(hipStream_t st, uint32_t D, uint32_t F, HashType h, u
 //   K_e(c)   = s^2 [pd2_e g_e sign_e(c) prod_{d!=e} w_d + sum_{o!=e} pd_e pd_o g_o sign_e sign_o prod_{d!=e,o} w_d]
 // so that dL/dgrid[c] += A_c dL/dy, dL/d(dL/dy) = sum_c A_c T[c], dL/dx_e = sum_c K_e(c) (T[c] . dL/dy)
 // (g = dL/d(dL/dx); the reference's per-edge loops regrouped per corner; fp32 throughout, grid
-// gradient by fp32 atomics). dLdy AoS fp16 [B][dy_stride]; dLddLdy AoS fp16 [B][ddy_stride] with
-// the padding columns zeroed; dx fp32 [B][D] overwritten.
+// gradient by fp32 atomics). dLdy AoS [B][dy_stride] and dLddLdy AoS [B][ddy_stride] (padding columns
+// zeroed) at the module's precision T; dx fp32 [B][D] overwritten.
 // ---------------------------------------------------------------------------------------------
-template <uint32_t D, uint32_t F, HashType H>
+template <uint32_t D, uint32_t F, HashType H, typename T>
 __global__ __launch_bounds__(256) void k_grid_bwd_bwd(uint32_t B, uint32_t L, const float* __restrict__ pos, uint32_t pstride,
-                                                      const _Float16* __restrict__ table, const float* __restrict__ gxx,
-                                                      const _Float16* __restrict__ dLdy, uint32_t dy_stride, float* __restrict__ grad,
-                                                      _Float16* __restrict__ dLddLdy, uint32_t ddy_stride, float* __restrict__ dx,
+                                                      const T* __restrict__ table, const float* __restrict__ gxx,
+                                                      const T* __restrict__ dLdy, uint32_t dy_stride, float* __restrict__ grad,
+                                                      T* __restrict__ dLddLdy, uint32_t ddy_stride, float* __restrict__ dx,
                                                       const LevelInfo* __restrict__ levels, uint32_t hash_grid, uint32_t interp_u,
                                                       const GridOpts o) {
 	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -536,20 +571,20 @@ __global__ __launch_bounds__(256) void k_grid_bwd_bwd(uint32_t B, uint32_t L, co
 		}
 		if (dLddLdy)
 #pragma unroll
-			for (uint32_t f = 0; f < F; ++f) dLddLdy[(size_t)i * ddy_stride + l * F + f] = f16_rn(fwd_masked ? 0.0f : ddy[f]);
+			for (uint32_t f = 0; f < F; ++f) dLddLdy[(size_t)i * ddy_stride + l * F + f] = enc_round<T>(fwd_masked ? 0.0f : ddy[f]);
 	}
 	if (dLddLdy)
-		for (uint32_t k = L * F; k < ddy_stride; ++k) dLddLdy[(size_t)i * ddy_stride + k] = (_Float16)0.0f;
+		for (uint32_t k = L * F; k < ddy_stride; ++k) dLddLdy[(size_t)i * ddy_stride + k] = (T)0.0f;
 	if (dx)
 #pragma unroll
 		for (uint32_t d = 0; d < D; ++d) dx[(size_t)i * D + d] = res[d];
 }
 
-template <uint32_t D, uint32_t F>
+template <uint32_t D, uint32_t F, typename T>
 static void grid_bwd_bwd_h(hipStream_t st, HashType h, dim3 g, uint32_t B, uint32_t L, const float* pos, uint32_t ps,
-                           const _Float16* t, const float* gx, const _Float16* dy, uint32_t dys, float* grad, _Float16* ddy,
+                           const T* t, const float* gx, const T* dy, uint32_t dys, float* grad, T* ddy,
                            uint32_t ddys, float* dx, const LevelInfo* lv, uint32_t hg, uint32_t in, const GridOpts& go) {
-#define GBB_LAUNCH(HH) hipLaunchKernelGGL((k_grid_bwd_bwd<D, F, HH>), g, dim3(256), 0, st, B, L, pos, ps, t, gx, dy, dys, grad, ddy, ddys, dx, lv, hg, in, go)
+#define GBB_LAUNCH(HH) hipLaunchKernelGGL((k_grid_bwd_bwd<D, F, HH, T>), g, dim3(256), 0, st, B, L, pos, ps, t, gx, dy, dys, grad, ddy, ddys, dx, lv, hg, in, go)
 	switch (h) {
 		case HashType::Prime: GBB_LAUNCH(HashType::Prime); break;
 		case HashType::ReversedPrime: GBB_LAUNCH(HashType::ReversedPrime); break;
@@ -558,36 +593,49 @@ static void grid_bwd_bwd_h(hipStream_t st, HashType h, dim3 g, uint32_t B, uint3
 #undef GBB_LAUNCH
 }
 
-template <uint32_t D>
+template <uint32_t D, typename T>
 static void grid_bwd_bwd_f(hipStream_t st, uint32_t F, HashType h, dim3 g, uint32_t B, uint32_t L, const float* pos, uint32_t ps,
-                           const _Float16* t, const float* gx, const _Float16* dy, uint32_t dys, float* grad, _Float16* ddy,
+                           const T* t, const float* gx, const T* dy, uint32_t dys, float* grad, T* ddy,
                            uint32_t ddys, float* dx, const LevelInfo* lv, uint32_t hg, uint32_t in, const GridOpts& go) {
 	switch (F) {
-		case 1: grid_bwd_bwd_h<D, 1>(st, h, g, B, L, pos, ps, t, gx, dy, dys, grad, ddy, ddys, dx, lv, hg, in, go); break;
-		case 2: grid_bwd_bwd_h<D, 2>(st, h, g, B, L, pos, ps, t, gx, dy, dys, grad, ddy, ddys, dx, lv, hg, in, go); break;
-		case 4: grid_bwd_bwd_h<D, 4>(st, h, g, B, L, pos, ps, t, gx, dy, dys, grad, ddy, ddys, dx, lv, hg, in, go); break;
-		case 8: grid_bwd_bwd_h<D, 8>(st, h, g, B, L, pos, ps, t, gx, dy, dys, grad, ddy, ddys, dx, lv, hg, in, go); break;
+		case 1: grid_bwd_bwd_h<D, 1, T>(st, h, g, B, L, pos, ps, t, gx, dy, dys, grad, ddy, ddys, dx, lv, hg, in, go); break;
+		case 2: grid_bwd_bwd_h<D, 2, T>(st, h, g, B, L, pos, ps, t, gx, dy, dys, grad, ddy, ddys, dx, lv, hg, in, go); break;
+		case 4: grid_bwd_bwd_h<D, 4, T>(st, h, g, B, L, pos, ps, t, gx, dy, dys, grad, ddy, ddys, dx, lv, hg, in, go); break;
+		case 8: grid_bwd_bwd_h<D, 8, T>(st, h, g, B, L, pos, ps, t, gx, dy, dys, grad, ddy, ddys, dx, lv, hg, in, go); break;
 		default: throw std::runtime_error("GridEncoding: n_features_per_level must be 1, 2, 4 or 8");
 	}
+}
+
+template <typename T>
+static void grid_bwd_bwd_t(hipStream_t st, uint32_t D, uint32_t F, HashType h, uint32_t B, uint32_t L, const float* pos, uint32_t pos_stride,
+                           const T* t, const float* dL_ddLdx, const T* dy, uint32_t dy_stride, float* grad32, T* ddy, uint32_t ddy_stride,
+                           float* dx, const LevelInfo* levels, bool hash_grid, Interp interp, const GridOpts& go) {
+	if (B == 0) return;
+	const dim3 g(div_round_up(B, 256));
+	const uint32_t hg = hash_grid ? 1u : 0u, in = (uint32_t)interp;
+	switch (D) {
+		case 2: grid_bwd_bwd_f<2, T>(st, F, h, g, B, L, pos, pos_stride, t, dL_ddLdx, dy, dy_stride, grad32, ddy, ddy_stride, dx, levels, hg, in, go); break;
+		case 3: grid_bwd_bwd_f<3, T>(st, F, h, g, B, L, pos, pos_stride, t, dL_ddLdx, dy, dy_stride, grad32, ddy, ddy_stride, dx, levels, hg, in, go); break;
+		case 4: grid_bwd_bwd_f<4, T>(st, F, h, g, B, L, pos, pos_stride, t, dL_ddLdx, dy, dy_stride, grad32, ddy, ddy_stride, dx, levels, hg, in, go); break;
+		default: throw std::runtime_error("GridEncoding: number of input dims must be 2, 3 or 4");
+	}
+	TCNN_HIP_CHECK(hipGetLastError());
 }
 
 void launch_grid_bwd_bwd(hipStream_t st, uint32_t D, uint32_t F, HashType h, uint32_t B, uint32_t L, const float* pos,
                          uint32_t pos_stride, const void* table16, const float* dL_ddLdx, const void* dLdy16, uint32_t dy_stride,
                          float* grad32, void* dLddLdy16, uint32_t ddy_stride, float* dx, const LevelInfo* levels, bool hash_grid,
                          Interp interp, const GridOpts& go) {
-	if (B == 0) return;
-	const dim3 g(div_round_up(B, 256));
-	const _Float16* t = (const _Float16*)table16;
-	const _Float16* dy = (const _Float16*)dLdy16;
-	_Float16* ddy = (_Float16*)dLddLdy16;
-	const uint32_t hg = hash_grid ? 1u : 0u, in = (uint32_t)interp;
-	switch (D) {
-		case 2: grid_bwd_bwd_f<2>(st, F, h, g, B, L, pos, pos_stride, t, dL_ddLdx, dy, dy_stride, grad32, ddy, ddy_stride, dx, levels, hg, in, go); break;
-		case 3: grid_bwd_bwd_f<3>(st, F, h, g, B, L, pos, pos_stride, t, dL_ddLdx, dy, dy_stride, grad32, ddy, ddy_stride, dx, levels, hg, in, go); break;
-		case 4: grid_bwd_bwd_f<4>(st, F, h, g, B, L, pos, pos_stride, t, dL_ddLdx, dy, dy_stride, grad32, ddy, ddy_stride, dx, levels, hg, in, go); break;
-		default: throw std::runtime_error("GridEncoding: number of input dims must be 2, 3 or 4");
-	}
-	TCNN_HIP_CHECK(hipGetLastError());
+	grid_bwd_bwd_t<_Float16>(st, D, F, h, B, L, pos, pos_stride, (const _Float16*)table16, dL_ddLdx, (const _Float16*)dLdy16, dy_stride, grad32,
+	                         (_Float16*)dLddLdy16, ddy_stride, dx, levels, hash_grid, interp, go);
+}
+
+void launch_grid_bwd_bwd_f32(hipStream_t st, uint32_t D, uint32_t F, HashType h, uint32_t B, uint32_t L, const float* pos,
+                             uint32_t pos_stride, const float* table32, const float* dL_ddLdx, const float* dLdy32, uint32_t dy_stride,
+                             float* grad32, float* dLddLdy32, uint32_t ddy_stride, float* dx, const LevelInfo* levels, bool hash_grid,
+                             Interp interp, const GridOpts& go) {
+	grid_bwd_bwd_t<float>(st, D, F, h, B, L, pos, pos_stride, table32, dL_ddLdx, dLdy32, dy_stride, grad32, dLddLdy32, ddy_stride, dx, levels,
+	                      hash_grid, interp, go);
 }
 
 // Diagnostic (TCNN_DEBUG_GRID_TIMES=1): per-workgroup start/end wall clock of the grid backward,

@@ -280,6 +280,8 @@ void launch_cast_f16_f32(hipStream_t st, const void* in, float* out, size_t n);
 // out = fp16(in / s), stored as fp16 or widened to fp32
 void launch_scale_f16(hipStream_t st, const void* in, void* out, float s, size_t n);
 void launch_div_f32(hipStream_t st, float* x, float s, size_t n);
+// out = in * s in fp32: dL/dy * loss_scale of an fp32 encoding module (its gradients take launch_div_f32)
+void launch_scale_f32(hipStream_t st, const float* in, float* out, float s, size_t n);
 void launch_div_f16(hipStream_t st, const void* in, void* out, float s, size_t n, bool out_f32);
 void launch_grad_finalize(hipStream_t st, const float* g, void* out, float s, size_t n, bool out_f32);
 
@@ -352,6 +354,38 @@ void launch_composite_fwd(hipStream_t st, uint32_t B, const float* x, void* out1
 // stores); dy16 AoS fp16 [B][dy_stride]
 void launch_composite_bwd_input(hipStream_t st, uint32_t B, const float* x, const void* dy16, uint32_t dy_stride, float* dx,
                                 const CompTable& t);
+
+// ---- fp32-precision encoding modules (Encoding dtype = float32; grid_f32.hip and the float
+// instantiations of the typed kernels in grid.hip, composite.hip, encodings.hip). Tables, encoded rows
+// AoS [B][stride], dL/dy and dL/d(dL/dy) are fp32 and nothing in between is narrowed to fp16. Same
+// arguments as the fp16 launchers above; dL/dy is always AoS rows. ----
+// only the value columns [0, L * F) of each row are written
+void launch_grid_fwd_f32(hipStream_t st, uint32_t D, uint32_t F, HashType h, uint32_t B, uint32_t L, const float* pos,
+                         uint32_t pos_stride, const float* table32, float* out32, uint32_t out_stride, const LevelInfo* levels,
+                         bool hash_grid, Interp interp, const GridOpts& opts = GridOpts{});
+// LDS-privatised backward: items with all F features (slabs in parameter order), partial [n_chunks][partial_stride]
+void launch_grid_bwd_f32(hipStream_t st, uint32_t D, uint32_t F, HashType h, uint32_t B, const float* pos, uint32_t pos_stride,
+                         const float* dLdy32, uint32_t dy_stride, const GridSlice* slices, uint32_t n_slices, uint32_t n_chunks,
+                         float* partial, uint32_t partial_stride, const LevelInfo* levels, bool hash_grid, Interp interp,
+                         const GridOpts& opts = GridOpts{});
+void launch_grid_bwd_input_f32(hipStream_t st, uint32_t D, uint32_t F, HashType h, uint32_t B, uint32_t L, const float* pos,
+                               uint32_t pos_stride, const float* table32, const float* dLdy32, uint32_t dy_stride, float* dx,
+                               uint32_t dx_stride, const LevelInfo* levels, bool hash_grid, Interp interp, const GridOpts& opts = GridOpts{});
+void launch_grid_bwd_bwd_f32(hipStream_t st, uint32_t D, uint32_t F, HashType h, uint32_t B, uint32_t L, const float* pos,
+                             uint32_t pos_stride, const float* table32, const float* dL_ddLdx, const float* dLdy32, uint32_t dy_stride,
+                             float* grad32, float* dLddLdy32, uint32_t ddy_stride, float* dx, const LevelInfo* levels, bool hash_grid,
+                             Interp interp, const GridOpts& opts = GridOpts{});
+void launch_oneblob_fwd_f32(hipStream_t st, uint32_t B, uint32_t D, uint32_t n_bins, const float* x, uint32_t x_stride, float* out32,
+                            uint32_t out_stride, uint32_t n_pad);
+void launch_oneblob_bwd_f32(hipStream_t st, uint32_t B, uint32_t D, uint32_t n_bins, const float* x, uint32_t x_stride,
+                            const float* dy32, uint32_t dy_stride, float* dx, uint32_t dx_stride);
+void launch_identity_fwd_f32(hipStream_t st, uint32_t B, uint32_t D, float scale, float offset, const float* x, uint32_t x_stride,
+                             float* out32, uint32_t out_stride, uint32_t n_pad);
+void launch_identity_bwd_f32(hipStream_t st, uint32_t B, uint32_t D, float scale, const float* dy32, uint32_t dy_stride, float* dx,
+                             uint32_t dx_stride);
+void launch_composite_fwd_f32(hipStream_t st, uint32_t B, const float* x, float* out32, const CompTable& t);
+void launch_composite_bwd_input_f32(hipStream_t st, uint32_t B, const float* x, const float* dy32, uint32_t dy_stride, float* dx,
+                                    const CompTable& t);
 
 void launch_probe_hfma(hipStream_t st, const void* a, const void* b, const void* c, void* out, uint32_t n_pairs);
 // Diagnostic: the config_hash fused (pipelined) kernel with s_memtime phase stamps (prof: [blocks*8][8] u64).

@@ -236,6 +236,10 @@ __global__ void k_scale_f16(const _Float16* __restrict__ in, _Float16* __restric
 	const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (i < n) out[i] = f16_rn((float)in[i] * s);
 }
+__global__ void k_scale_f32(const float* __restrict__ in, float* __restrict__ out, float s, size_t n) {
+	const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i < n) out[i] = in[i] * s;
+}
 __global__ void k_div_f32(float* __restrict__ x, float s, size_t n) {
 	const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (i < n) x[i] = x[i] / s;
@@ -263,6 +267,11 @@ void launch_grad_finalize(hipStream_t st, const float* g, void* out, float s, si
 void launch_scale_f16(hipStream_t st, const void* in, void* out, float s, size_t n) {
 	if (!n) return;
 	hipLaunchKernelGGL(k_scale_f16, dim3(div_round_up(n, 256)), dim3(256), 0, st, (const _Float16*)in, (_Float16*)out, s, n);
+	TCNN_HIP_CHECK(hipGetLastError());
+}
+void launch_scale_f32(hipStream_t st, const float* in, float* out, float s, size_t n) {
+	if (!n) return;
+	hipLaunchKernelGGL(k_scale_f32, dim3(div_round_up(n, 256)), dim3(256), 0, st, in, out, s, n);
 	TCNN_HIP_CHECK(hipGetLastError());
 }
 void launch_div_f32(hipStream_t st, float* x, float s, size_t n) {

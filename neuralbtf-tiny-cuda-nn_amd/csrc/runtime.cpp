@@ -394,6 +394,69 @@ void GridEncodingHost::backward_backward_input(hipStream_t st, uint32_t B, const
 	                    dL_ddLdx, dy16, dy_stride, grad32, dLddLdy16, ddy_stride, dx, dev_levels(), hash_grid(), desc.interp, opts());
 }
 
+// fp32 modules: every level as LDS items with all F features. A level whose F features fit the LDS
+// budget is one item; a larger hashed power-of-two level splits into power-of-two entry ranges
+// (IDX_HASH_RANGE), any other large level (dense, tiled) into ranges of S / F entries (the generic index,
+// corners outside the range skipped). Every item of a split level walks all of the chunk's points.
+void GridEncodingHost::build_plan_f32() {
+	if (!plan_f32.slices.empty()) return;
+	const uint32_t S = grid_bwd_slot_budget(), F = desc.n_features_per_level;
+	std::vector<GridSlice>& out = plan_f32.slices;
+	for (uint32_t l = 0; l < desc.n_levels; ++l) {
+		const uint32_t size = levels[l].size;
+		if ((uint64_t)size * F <= S) {
+			out.push_back(GridSlice{l, 0, size, 0, F});
+			continue;
+		}
+		uint32_t len = S / F;  // entries of one range (S and F are powers of two)
+		if ((size & (size - 1)) == 0) len = std::min(len, size);
+		for (uint32_t b = 0; b < size; b += len) out.push_back(GridSlice{l, b, std::min(size, b + len), 0, F});
+	}
+	for (const GridSlice& s : out) TCNN_CHECK((uint64_t)(s.end - s.begin) * F <= S, "GridEncoding: fp32 backward item exceeds the LDS");
+	plan_f32.identity = true;
+	plan_f32.d_slices.reserve(out.size() * sizeof(GridSlice));
+	TCNN_HIP_CHECK(hipMemcpy(plan_f32.d_slices.p, out.data(), out.size() * sizeof(GridSlice), hipMemcpyHostToDevice));
+}
+
+void GridEncodingHost::forward_f32(hipStream_t st, uint32_t B, const float* pos, uint32_t pos_stride, const float* table32, float* out32,
+                                   uint32_t out_stride) const {
+	launch_grid_fwd_f32(st, desc.n_pos_dims, desc.n_features_per_level, desc.hash_type, B, desc.n_levels, pos, pos_stride, table32, out32,
+	                    out_stride, dev_levels(), hash_grid(), desc.interp, opts());
+}
+
+void GridEncodingHost::backward_f32(hipStream_t st, GridBwdBufs& w, uint32_t B, const float* pos, uint32_t pstride, const float* dy32,
+                                    uint32_t dy_stride, float* grad32) const {
+	TCNN_CHECK(!plan_f32.slices.empty(), "GridEncoding: the fp32 backward plan was not built");
+	if (B == 0) {  // no points: zero gradient (Overwrite)
+		TCNN_HIP_CHECK(hipMemsetAsync(grad32, 0, (size_t)n_params * 4, st));
+		return;
+	}
+	const uint32_t n_chunks = bwd_chunks_f32(B);
+	// one chunk: its slab is the gradient (every parameter belongs to exactly one item, which writes it)
+	float* partial = grad32;
+	if (n_chunks > 1) {
+		w.partial.reserve((size_t)n_chunks * n_params * 4);
+		partial = w.partial.as<float>();
+	}
+	launch_grid_bwd_f32(st, desc.n_pos_dims, desc.n_features_per_level, desc.hash_type, B, pos, pstride, dy32, dy_stride,
+	                    plan_f32.d_slices.as<GridSlice>(), (uint32_t)plan_f32.slices.size(), n_chunks, partial, n_params, dev_levels(),
+	                    hash_grid(), desc.interp, opts());
+	if (n_chunks > 1) launch_grid_slab_reduce(st, partial, n_chunks, n_params, n_params, grad32, nullptr);
+}
+
+void GridEncodingHost::backward_input_f32(hipStream_t st, uint32_t B, const float* pos, uint32_t pos_stride, const float* table32,
+                                          const float* dy32, uint32_t dy_stride, float* dx, uint32_t dx_stride) const {
+	launch_grid_bwd_input_f32(st, desc.n_pos_dims, desc.n_features_per_level, desc.hash_type, B, desc.n_levels, pos, pos_stride, table32,
+	                          dy32, dy_stride, dx, dx_stride, dev_levels(), hash_grid(), desc.interp, opts());
+}
+
+void GridEncodingHost::backward_backward_input_f32(hipStream_t st, uint32_t B, const float* pos, uint32_t pos_stride, const float* table32,
+                                                   const float* dL_ddLdx, const float* dy32, uint32_t dy_stride, float* grad32,
+                                                   float* dLddLdy32, uint32_t ddy_stride, float* dx) const {
+	launch_grid_bwd_bwd_f32(st, desc.n_pos_dims, desc.n_features_per_level, desc.hash_type, B, desc.n_levels, pos, pos_stride, table32,
+	                        dL_ddLdx, dy32, dy_stride, grad32, dLddLdy32, ddy_stride, dx, dev_levels(), hash_grid(), desc.interp, opts());
+}
+
 static const char* grid_type_str(GridType t) { return t == GridType::Hash ? "Hash" : t == GridType::Dense ? "Dense" : "Tiled"; }
 static const char* hash_str(HashType t) { return t == HashType::Prime ? "Prime" : t == HashType::ReversedPrime ? "ReversedPrime" : "CoherentPrime"; }
 static const char* interp_str(Interp t) { return t == Interp::Nearest ? "Nearest" : t == Interp::Smoothstep ? "Smoothstep" : "Linear"; }
@@ -505,7 +568,7 @@ bool EncodingHost::known(const std::string& eo) {
 	       is_composite_otype(eo);
 }
 
-EncodingHost::EncodingHost(uint32_t n_dims_to_encode, const json& enc) : n_dims(n_dims_to_encode) {
+EncodingHost::EncodingHost(uint32_t n_dims_to_encode, const json& enc, bool fp32) : n_dims(n_dims_to_encode), f32(fp32) {
 	const std::string eo = jval<std::string>(enc, "otype", "OneBlob");  // encoding.cu:133
 	TCNN_CHECK(known(eo), "Encoding '" + eo + "' is not implemented by the MI355X engine yet");
 	if (ieq(eo, "Composite")) {
@@ -606,7 +669,9 @@ void EncodingHost::add_part(uint32_t n_in, uint32_t in_col, const json& enc) {
 		p.grid = std::make_unique<GridEncodingHost>(n_in, enc);
 		p.bufs = std::make_unique<GridBwdBufs>();
 		p.n_values = p.grid->n_features;
+		if (f32) p.grid->build_plan_f32();
 	}
+	p.f32 = f32;
 	parts.push_back(std::move(p));
 }
 
@@ -700,6 +765,15 @@ json EncodingHost::hyperparams() const {
 
 void EncodingHost::Part::forward(hipStream_t st, uint32_t B, const float* x, uint32_t x_stride, const void* params16, void* out16,
                                  uint32_t stride, bool alone) const {
+	if (f32) {  // the same part at fp32: fp32 parameters and rows
+		float* o = (float*)out16 + out_col;
+		if (kind == COMP_ONEBLOB) return launch_oneblob_fwd_f32(st, B, n_in, p0, x + in_col, x_stride, o, stride, width - n_values);
+		if (kind == COMP_IDENTITY) return launch_identity_fwd_f32(st, B, n_in, f0, f1, x + in_col, x_stride, o, stride, width - n_values);
+		TCNN_CHECK(kind == COMP_GRID, "this encoding has no kernel of its own");
+		TCNN_CHECK(params16, "grid forward needs the grid parameters");
+		if (alone && width > n_values) TCNN_HIP_CHECK(hipMemsetAsync(out16, 0, (size_t)B * stride * 4, st));
+		return grid->forward_f32(st, B, x + in_col, x_stride, (const float*)params16 + param_offset, o, stride);
+	}
 	_Float16* out = (_Float16*)out16 + out_col;
 	if (kind == COMP_ONEBLOB) return launch_oneblob_fwd(st, B, n_in, p0, x + in_col, x_stride, out, stride, width - n_values);
 	if (kind == COMP_IDENTITY) return launch_identity_fwd(st, B, n_in, f0, f1, x + in_col, x_stride, out, stride, width - n_values);
@@ -711,6 +785,15 @@ void EncodingHost::Part::forward(hipStream_t st, uint32_t B, const float* x, uin
 
 void EncodingHost::Part::backward_input(hipStream_t st, uint32_t B, const float* x, uint32_t x_stride, const void* params16,
                                         const void* dy16, int dy_layout, uint32_t stride, float* dx) const {
+	if (f32) {
+		const float* g = (const float*)dy16 + out_col;
+		TCNN_CHECK(dy_layout == 2, "an fp32 encoding reads dL/d(encoding) as AoS rows");
+		if (kind == COMP_ONEBLOB) return launch_oneblob_bwd_f32(st, B, n_in, p0, x + in_col, x_stride, g, stride, dx + in_col, x_stride);
+		if (kind == COMP_IDENTITY) return launch_identity_bwd_f32(st, B, n_in, f0, g, stride, dx + in_col, x_stride);
+		TCNN_CHECK(kind == COMP_GRID, "this encoding has no kernel of its own");
+		TCNN_CHECK(params16, "grid backward_input needs the grid parameters");
+		return grid->backward_input_f32(st, B, x + in_col, x_stride, (const float*)params16 + param_offset, g, stride, dx + in_col, x_stride);
+	}
 	const _Float16* dy = (const _Float16*)dy16 + out_col;
 	if (kind == COMP_ONEBLOB) return launch_oneblob_bwd(st, B, n_in, p0, x + in_col, x_stride, dy, stride, dx + in_col, x_stride);
 	if (kind == COMP_IDENTITY) return launch_identity_bwd(st, B, n_in, f0, dy, stride, dx + in_col, x_stride);
@@ -723,7 +806,8 @@ void EncodingHost::forward_aos(hipStream_t st, uint32_t B, const float* x, const
 	const uint32_t W = padded_output_width();
 	if (const Part* p = lone_part()) return p->forward(st, B, x, n_dims, params16, out16, W, true);
 	// one launch for every parameter-free value and all padding; each grid its own column slice
-	launch_composite_fwd(st, B, x, out16, table);
+	if (f32) launch_composite_fwd_f32(st, B, x, (float*)out16, table);
+	else launch_composite_fwd(st, B, x, out16, table);
 	for (const Part& p : parts)
 		if (p.grid) p.forward(st, B, x, n_dims, params16, out16, W, false);
 }
@@ -733,7 +817,8 @@ void EncodingHost::backward_input(hipStream_t st, uint32_t B, const float* x, co
 	const uint32_t W = padded_output_width();
 	TCNN_CHECK(dy_layout == 2 || lone_grid(), "backward_input reads dL/d(encoding) as AoS rows");
 	if (const Part* p = lone_part()) return p->backward_input(st, B, x, n_dims, params16, dy16, dy_layout, W, dx);
-	launch_composite_bwd_input(st, B, x, dy16, W, dx, table);
+	if (f32) launch_composite_bwd_input_f32(st, B, x, (const float*)dy16, W, dx, table);
+	else launch_composite_bwd_input(st, B, x, dy16, W, dx, table);
 	for (const Part& p : parts)
 		if (p.grid) p.backward_input(st, B, x, n_dims, params16, dy16, 2, W, dx);
 }
@@ -741,9 +826,11 @@ void EncodingHost::backward_input(hipStream_t st, uint32_t B, const float* x, co
 void EncodingHost::backward_params(hipStream_t st, uint32_t B, const float* x, const void* dy16, int dy_layout, float* grad32) const {
 	const uint32_t W = padded_output_width();
 	TCNN_CHECK(dy_layout == 2 || lone_grid(), "backward_params reads dL/d(encoding) as AoS rows");
-	for (const Part& p : parts)
-		if (p.grid)
-			p.grid->backward(st, *p.bufs, B, x + p.in_col, n_dims, (const _Float16*)dy16 + p.out_col, dy_layout, W, grad32 + p.param_offset);
+	for (const Part& p : parts) {
+		if (!p.grid) continue;
+		if (f32) p.grid->backward_f32(st, *p.bufs, B, x + p.in_col, n_dims, (const float*)dy16 + p.out_col, W, grad32 + p.param_offset);
+		else p.grid->backward(st, *p.bufs, B, x + p.in_col, n_dims, (const _Float16*)dy16 + p.out_col, dy_layout, W, grad32 + p.param_offset);
+	}
 }
 
 // ------------------------------------------------------------------------------------------

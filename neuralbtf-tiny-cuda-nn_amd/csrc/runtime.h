@@ -182,6 +182,28 @@ struct GridEncodingHost {
 	void backward_backward_input(hipStream_t st, uint32_t B, const float* pos, uint32_t pos_stride, const void* table16,
 	                             const float* dL_ddLdx, const void* dy16, uint32_t dy_stride, float* grad32, void* dLddLdy16,
 	                             uint32_t ddy_stride, float* dx) const;
+
+	// ---- fp32 precision (an fp32 encoding module: fp32 table, AoS fp32 rows and dL/dy; grid_f32.hip) ----
+	// The backward's work plan: EVERY level as LDS items holding all F features -- whole levels, or entry
+	// ranges of the levels too large for the LDS (those the fp16 path bins: the binned backward packs fp16
+	// into its records and has no fp32 form). Slabs are in parameter order. Built by build_plan_f32().
+	GridPlan plan_f32;
+	void build_plan_f32();
+	// point chunks: items x chunks in one round on the CUs, >= 8192 points each (as bwd_chunks)
+	uint32_t bwd_chunks_f32(uint32_t B) const {
+		const uint32_t n_items = std::max<uint32_t>(1u, (uint32_t)plan_f32.slices.size());
+		return std::max(1u, std::min(std::min(std::max(256u / n_items, 1u), 32u), B / 8192));
+	}
+	void forward_f32(hipStream_t st, uint32_t B, const float* pos, uint32_t pos_stride, const float* table32, float* out32,
+	                 uint32_t out_stride) const;
+	// the fp32 gradient of every grid parameter into grad32 [n_params], bit-reproducible
+	void backward_f32(hipStream_t st, GridBwdBufs& w, uint32_t B, const float* pos, uint32_t pstride, const float* dy32, uint32_t dy_stride,
+	                  float* grad32) const;
+	void backward_input_f32(hipStream_t st, uint32_t B, const float* pos, uint32_t pos_stride, const float* table32, const float* dy32,
+	                        uint32_t dy_stride, float* dx, uint32_t dx_stride) const;
+	void backward_backward_input_f32(hipStream_t st, uint32_t B, const float* pos, uint32_t pos_stride, const float* table32,
+	                                 const float* dL_ddLdx, const float* dy32, uint32_t dy_stride, float* grad32, float* dLddLdy32,
+	                                 uint32_t ddy_stride, float* dx) const;
 };
 
 // ---- fully fused MLP shape (reference networks/fully_fused_mlp.h) ----
@@ -215,6 +237,11 @@ struct AdamHost {
 // encoding runs the composite kernels (composite.hip), then each nested grid on its column slice.
 struct EncodingHost {
 	uint32_t n_dims = 0;  // input dims encoded
+	// Precision of the parameters, the encoded rows and dL/dy (create_encoding<T>): fp16, or fp32 for an
+	// fp32 encoding module, whose every buffer named "16" below then holds fp32 and whose kernels are the
+	// fp32 ones (nothing narrowed to fp16). Layout, widths, alignment, parameter offsets, initial
+	// parameters, hyperparams() and name() do not depend on it. Networks always build fp16 encodings.
+	bool f32 = false;
 
 	// Widths follow composite.h:188-198: every part is created with alignment 1, part i is widened so
 	// that part i + 1 starts at a multiple of its required alignment (a grid's n_features_per_level,
@@ -228,12 +255,13 @@ struct EncodingHost {
 		uint32_t param_offset = 0;   // of a grid's table inside the encoding's parameters
 		std::unique_ptr<GridEncodingHost> grid;
 		std::unique_ptr<GridBwdBufs> bufs;  // scratch of this grid's backward
+		bool f32 = false;                   // the encoding's precision (EncodingHost::f32)
 		uint32_t required_alignment() const { return grid ? grid->desc.n_features_per_level : 1u; }
 		bool own_kernel() const { return kind == COMP_GRID || kind == COMP_ONEBLOB || kind == COMP_IDENTITY; }
 		json hyperparams() const;
 		// This part's own kernel on its column slice. x, params16, out16 / dy16 and dx are the
-		// encoding's: fp32 [B][x_stride], the parameters, AoS fp16 rows of `stride` columns, fp32
-		// [B][x_stride]. alone: the part owns the whole row (a grid then zeroes it for its padding).
+		// encoding's: fp32 [B][x_stride], the parameters, AoS rows of `stride` columns (fp16; fp32 when
+		// f32, like the parameters), fp32 [B][x_stride]. alone: the part owns the whole row (a grid then zeroes it for its padding).
 		void forward(hipStream_t st, uint32_t B, const float* x, uint32_t x_stride, const void* params16, void* out16, uint32_t stride,
 		             bool alone) const;
 		void backward_input(hipStream_t st, uint32_t B, const float* x, uint32_t x_stride, const void* params16, const void* dy16,
@@ -244,7 +272,7 @@ struct EncodingHost {
 	CompTable table{};  // the parts as the composite kernels read them (encodings that run them only)
 	uint32_t n_grid_params = 0;
 
-	EncodingHost(uint32_t n_dims_to_encode, const json& enc);
+	EncodingHost(uint32_t n_dims_to_encode, const json& enc, bool fp32 = false);
 	static bool known(const std::string& otype);
 	static bool is_grid_otype(const std::string& otype);
 	// the part that stands alone and runs its own kernel; nullptr: the composite kernels run
@@ -257,7 +285,7 @@ struct EncodingHost {
 	json hyperparams() const;
 	// the reference's class name (SphericalHarmonicsEncoding, CompositeEncoding, ...)
 	std::string name() const { return otype + "Encoding"; }
-	// encoded output AoS fp16 [B][padded_output_width()] (padding: grid 0, OneBlob / Identity /
+	// encoded output AoS fp16 (fp32 when f32) [B][padded_output_width()] (padding: grid 0, OneBlob / Identity /
 	// TriangleWave 1 after the values, SphericalHarmonics 1 before them)
 	void forward_aos(hipStream_t st, uint32_t B, const float* x, const void* params16, void* out16) const;
 	// The layout the backward reads dL/d(encoding) fp16 in (launch_grid_bwd): AoS [B][padded width]
@@ -265,14 +293,14 @@ struct EncodingHost {
 	// its backward reads coalesced (AoS rows would cost one 64-byte line per 4-byte read)
 	int dy_layout() const {
 		const GridEncodingHost* g = lone_grid();
-		return g && g->desc.n_features_per_level == 2 && g->n_to_pad == 0 ? 0 : 2;
+		return !f32 && g && g->desc.n_features_per_level == 2 && g->n_to_pad == 0 ? 0 : 2;
 	}
 	// dL/dx fp32 [B][n_dims]; params16 = the encoding's parameters (grids). dy_layout: 2, or what
 	// dy_layout() allows
 	void backward_input(hipStream_t st, uint32_t B, const float* x, const void* dy16, float* dx, const void* params16 = nullptr,
 	                    int dy_layout = 2) const;
 	// the fp32 gradient of every grid's table into grad32 [n_params()] (each grid's slice in order),
-	// each grid with its own scratch
+	// each grid with its own scratch (an fp32 encoding: this is its dL/dparams, written in place)
 	void backward_params(hipStream_t st, uint32_t B, const float* x, const void* dy16, int dy_layout, float* grad32) const;
 
 private:
