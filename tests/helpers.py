@@ -66,6 +66,74 @@ def trainer_arrays(t):
     }
 
 
+ADAM_ARRAYS = ("w32", "w16", "m1", "m2", "steps")
+
+
+def fresh_adam_state(w32):
+    """the optimizer state of a new trainer with masters w32 (fp16 copies rounded from them, zero moments)"""
+    w32 = np.array(w32, np.float32)
+    n = w32.size
+    return {"w32": w32, "w16": O.f2h(w32), "m1": np.zeros(n, np.float32), "m2": np.zeros(n, np.float32),
+            "steps": np.zeros(n, np.uint32)}
+
+
+def oracle_adam_step(opt, n_matrix, loss_scale, global_step, state, g16):
+    """One step of the oracle's Adam (optimizer block opt, global_step = the optimizer's step count after its
+    increment) on state (ADAM_ARRAYS, updated in place) with the fp16 gradient bits g16."""
+    O.adam_step(O.adam_cfg(opt), n_matrix, float(loss_scale), int(global_step), state["w32"], state["w16"],
+                np.ascontiguousarray(g16, np.uint16), state["m1"], state["m2"], state["steps"])
+
+
+def bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view({2: np.uint16, 4: np.uint32}[a.dtype.itemsize])
+
+
+def adam_arrays(t):
+    """the trainer's Adam arrays on the host: ADAM_ARRAYS and the fp16 gradients g16"""
+    a = trainer_arrays(t)
+    m1, m2, st = (x.cpu().numpy() for x in t.optimizer_state())
+    return {"w32": a["w32"], "w16": a["w16"], "g16": a["g16"], "m1": m1, "m2": m2, "steps": st.view(np.uint32)}
+
+
+def assert_adam_bits(got, ref, what, names=ADAM_ARRAYS, where=None):
+    """got[k] and ref[k] bit-identical for every k of names (on the elements where, if given)"""
+    for k in names:
+        g, r = bits(got[k]), bits(ref[k])
+        if where is not None:
+            g, r = g[where], r[where]
+        bad = np.flatnonzero(g != r)
+        # (what, array, mismatches, first mismatching index, got bits, expected bits)
+        assert bad.size == 0, (what, k, int(bad.size), int(bad[0]), hex(int(g[bad[0]])), hex(int(r[bad[0]])))
+
+
+def oracle_grad16(cfg, w16, pos, tgt, loss_scale=128.0, n_threads=4):
+    """fp16 parameter gradients (bits) of one oracle training step of cfg (a 32-column grid encoding or OneBlob,
+    ReLU MLP, RelativeL2) at fp16 parameters w16, with the loss scaled by loss_scale: what OracleModel.train_step
+    leaves in grad16 at its fixed loss scale of 128."""
+    enc_cfg, net = cfg["encoding"], cfg["network"]
+    W, NH = net["n_neurons"], net["n_hidden_layers"]
+    w16 = np.asarray(w16, np.uint16)
+    if enc_cfg["otype"].lower() == "oneblob":
+        D, nb = pos.shape[1], enc_cfg["n_bins"]
+        IN = (D * nb + 15) // 16 * 16
+        nm = O.mlp_n_params(W, IN, NH, 16)
+        enc = O.oneblob_fwd(pos, nb, IN - D * nb)
+        out16, hidden = O.mlp_fwd(W, IN, NH, 16, w16[:nm], enc, input_soa=False, n_threads=n_threads)
+        _, dout, _ = O.relative_l2(out16, tgt, loss_scale=loss_scale)
+        wg, _ = O.mlp_bwd(W, IN, NH, 16, w16[:nm], enc, hidden, dout, input_soa=False, want_dinput=False, n_threads=n_threads)
+        return O.f2h(wg)
+    g = O.grid_cfg(enc_cfg, pos.shape[1])
+    IN = g.n_levels * g.n_features_per_level
+    assert IN % 16 == 0
+    nm = O.mlp_n_params(W, IN, NH, 16)
+    enc = O.grid_fwd(g, pos, w16[nm:])
+    out16, hidden = O.mlp_fwd(W, IN, NH, 16, w16[:nm], enc, n_threads=n_threads)
+    _, dout, _ = O.relative_l2(out16, tgt, loss_scale=loss_scale)
+    wg, denc = O.mlp_bwd(W, IN, NH, 16, w16[:nm], enc, hidden, dout, n_threads=n_threads)
+    return O.f2h(np.concatenate([wg, O.grid_bwd(g, pos, denc)]))
+
+
 def rel_err(a, b):
     a = np.asarray(a, dtype=np.float64)
     b = np.asarray(b, dtype=np.float64)
