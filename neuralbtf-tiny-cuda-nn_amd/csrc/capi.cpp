@@ -2,6 +2,7 @@
 // codes + tcnn_last_error().
 #include "../../include/tcnn_mi355x.h"
 #include "debug_api.h"  // test-only diagnostics, not in the product header
+#include "debug_grid_bwd.h"
 
 #include <algorithm>
 #include <cstring>
@@ -776,6 +777,46 @@ int tcnn_debug_fused_phase_cycles(tcnn_trainer* t, void* stream, uint32_t n, con
 			for (size_t w = 0; w < (size_t)nb * WV; ++w) sum += h[w * 16 + k];
 			host_cycles8[k] = sum;
 		}
+	});
+}
+
+int tcnn_debug_grid_bwd_count_fallbacks(int on) {
+	return guard([&] { grid_bwd_debug_count_fallbacks(on != 0); });
+}
+int tcnn_debug_grid_bwd_fallbacks(uint32_t* count) {
+	return guard([&] { *count = grid_bwd_debug_fallbacks(); });
+}
+int tcnn_debug_step_dldenc(tcnn_trainer* t, void* host_dldenc, size_t dldenc_bytes, float* host_bound, size_t bound_bytes,
+                           int* bound_live) {
+	return guard([&] {
+		auto& ws = t->t->ws;
+		TCNN_HIP_CHECK(hipDeviceSynchronize());
+		TCNN_CHECK(dldenc_bytes <= ws.dLdenc.bytes, "debug: dL/d(encoding) read past the workspace");
+		TCNN_HIP_CHECK(hipMemcpy(host_dldenc, ws.dLdenc.p, dldenc_bytes, hipMemcpyDeviceToHost));
+		*bound_live = ws.dy_bound_live ? 1 : 0;
+		if (ws.dy_bound_live) {
+			TCNN_CHECK(bound_bytes <= ws.dy_bound.bytes, "debug: slice sums read past the workspace");
+			TCNN_HIP_CHECK(hipMemcpy(host_bound, ws.dy_bound.p, bound_bytes, hipMemcpyDeviceToHost));
+		}
+	});
+}
+int tcnn_debug_grid_backward_items(tcnn_trainer* t, void* stream, uint32_t n, const float* input, const void* dldy_pairs,
+                                   const float* dy_bound, float* host_slabs, size_t slab_floats, uint32_t* n_chunks,
+                                   uint32_t* slab_stride) {
+	return guard([&] {
+		auto& tr = *t->t;
+		TCNN_CHECK(tr.model->grid != nullptr, "debug: trainer model has no grid encoding");
+		TCNN_CHECK(n % 32 == 0, "debug: batch must be a multiple of 32");
+		GridEncodingHost& g = *tr.model->grid;
+		hipStream_t st = (hipStream_t)stream;
+		GridBwdBufs w;
+		g.backward_items(st, w, n, input, g.desc.n_pos_dims, dldy_pairs, 0, 0, nullptr, 0, dy_bound);
+		TCNN_HIP_CHECK(hipStreamSynchronize(st));
+		*n_chunks = w.n_chunks;
+		*slab_stride = g.n_lds_params;
+		const size_t nfl = (size_t)w.n_chunks * g.n_lds_params;
+		TCNN_CHECK(nfl <= slab_floats, "debug: slab buffer too small");
+		TCNN_HIP_CHECK(hipMemcpy(host_slabs, w.partial.p, nfl * 4, hipMemcpyDeviceToHost));
 	});
 }
 

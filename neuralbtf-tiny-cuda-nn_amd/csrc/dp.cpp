@@ -160,7 +160,7 @@ void TrainerHost::training_step_dp(hipStream_t st, uint32_t B, const float* inpu
 	float* g = g32.as<float>();
 	mark(st, 0);
 	if (overlapped_ok()) {
-		m.fused_kernel(st, ws, B, input, target, n_output_dims, loss_scale, w16.p, false);
+		m.fused_kernel(st, ws, B, input, target, n_output_dims, loss_scale, w16.p, false, nullptr, nullptr, nullptr, true);
 		launch_column_sums(st, ws.wgrad_partial.as<float>(), ws.n_fused_blocks, (uint32_t)n_mlp, g);
 		launch_sum(st, ws.loss_partial.as<float>(), ws.n_loss_partials, d_loss.as<float>());
 		if (!dp_sharded) {  // the network part travels while the grid backward runs

@@ -126,7 +126,7 @@ void launch_fused_train(hipStream_t st, uint32_t W, uint32_t IN, uint32_t NH, ui
                         const float* pos, const float* target, void* out16, void* dLdenc_pairs,
                         float* wgrad_partial, float* loss_partial, const LevelInfo* levels, bool hash_grid,
                         Interp interp, uint32_t n_blocks, const void* dout16, const void* wimage, uint32_t loss_l2,
-                        bool inrange_index, const void* enc16, float dout_scale) {
+                        bool inrange_index, const void* enc16, float dout_scale, float* dy_bound) {
 	TCNN_CHECK(B % 32 == 0, "fused train: batch must be a multiple of 32");
 	TCNN_CHECK(wimage || ((uintptr_t)params16 & 15) == 0, "fused train: parameters must be 16-byte aligned");
 	FusedTrainArgs a;
@@ -152,6 +152,8 @@ void launch_fused_train(hipStream_t st, uint32_t W, uint32_t IN, uint32_t NH, ui
 	a.hash_grid = hash_grid ? 1u : 0u;
 	a.interp = (uint32_t)interp;
 	a.prof = nullptr;
+	TCNN_CHECK(!dy_bound || (!dout16 && !enc16), "fused train: slice sums only with the loss inside and the encoding gathered");
+	a.dy_bound = dy_bound;
 #define X(w, in, nh) if (W == w && IN == in && NH == nh) { launch_fused_shape<w, in, nh>(st, D, h, act, a, n_blocks); return; }
 	TCNN_FUSED_SHAPES(X)
 #undef X

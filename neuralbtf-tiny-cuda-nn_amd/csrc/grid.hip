@@ -648,6 +648,17 @@ static bool dbg_grid_times() {
 
 uint32_t grid_bwd_slot_budget() { return GRID_BWD_SLOTS; }
 
+static DevBufLite g_fallbacks;
+static bool g_count_fallbacks = false;
+void grid_bwd_debug_count_fallbacks(bool on) { g_count_fallbacks = on; }
+uint32_t grid_bwd_debug_fallbacks() {
+	uint32_t n = 0;
+	if (!g_fallbacks.p) return 0;
+	TCNN_HIP_CHECK(hipDeviceSynchronize());
+	TCNN_HIP_CHECK(hipMemcpy(&n, g_fallbacks.p, 4, hipMemcpyDeviceToHost));
+	return n;
+}
+
 extern template void grid_bwd_f<2>(hipStream_t, uint32_t, HashType, int, uint32_t, dim3, size_t, uint32_t, const float*, uint32_t,
                                    const _Float16*, const GridSlice*, float*, uint32_t, const LevelInfo*, uint32_t, uint32_t, uint32_t,
                                    const GridBwdLaunch&);
@@ -662,7 +673,7 @@ void launch_grid_bwd(hipStream_t st, uint32_t D, uint32_t F, HashType h, uint32_
                      uint32_t pos_stride, const void* dLdy16, int dy_layout, uint32_t dy_stride, const GridSlice* slices,
                      uint32_t n_slices, uint32_t n_chunks, float* partial, uint32_t partial_stride,
                      const LevelInfo* levels, bool hash_grid, Interp interp, const GridBwdEpilogue* ep, const GridOpts& go,
-                     const GridSlice* host_slices, const LevelInfo* host_levels, uint32_t n_levels) {
+                     const GridSlice* host_slices, const LevelInfo* host_levels, uint32_t n_levels, const float* dy_bound) {
 	const uint32_t n_tail = (ep && ep->enabled) ? ep->n_mlp_groups : 0u;
 	if (n_tail == 0 && (n_slices == 0 || B == 0)) return;  // callers zero the gradient of empty batches
 	if (B == 0) n_slices = 0;
@@ -674,6 +685,12 @@ void launch_grid_bwd(hipStream_t st, uint32_t D, uint32_t F, HashType h, uint32_
 	else gl.ep.enabled = 0;
 	gl.dbg_times = nullptr;
 	gl.opts = go;
+	gl.dy_bound = dy_layout == 0 ? dy_bound : nullptr;
+	gl.fallback_count = nullptr;
+	if (g_count_fallbacks) {
+		gl.fallback_count = (uint32_t*)g_fallbacks.get(4);
+		TCNN_HIP_CHECK(hipMemsetAsync(gl.fallback_count, 0, 4, st));
+	}
 	gl.tb.n_items = gl.tb.n_levels = 0;
 	if (host_slices && host_levels && n_slices <= GRID_BWD_ARG_ITEMS && n_levels <= GRID_BWD_ARG_LEVELS) {
 		gl.tb.n_items = n_slices;

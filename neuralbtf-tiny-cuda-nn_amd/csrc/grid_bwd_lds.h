@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "adam_device.h"
+#include "grid_bwd_scale.h"
 #include "grid_device.h"
 
 namespace tcnn_amd {
@@ -199,8 +200,22 @@ __device__ __forceinline__ void load_pos_batch(const float* __restrict__ pos, ui
 	}
 }
 
-template <uint32_t D, uint32_t F, HashType H, int KIND, int MODE>
-__device__ __forceinline__ void grid_bwd_points_regs(const uint32_t (&dyb)[GRID_BWD_PR], const float (&xs0)[GRID_BWD_PU][D],
+// The dL/dy bits (layout 0, F == 2) of batch k, beside its positions.
+__device__ __forceinline__ void load_dy_batch(const uint32_t* __restrict__ dy_lv, uint32_t i0, uint32_t i1, uint32_t k,
+                                              uint32_t (&dst)[GRID_BWD_PU]) {
+#pragma unroll
+	for (uint32_t u = 0; u < GRID_BWD_PU; ++u) {
+		const uint32_t i = i0 + threadIdx.x + (k * GRID_BWD_PU + u) * blockDim.x;
+		dst[u] = i < i1 ? dy_lv[i] : 0u;
+	}
+}
+
+// STREAM: dyb holds only the first batch (slots 0 .. GRID_BWD_PU-1); the dL/dy bits of batch k + 1
+// are loaded from dy_lv (the level's [B] half2 row) together with its positions while batch k is
+// accumulated -- plain loads, the compiler places the waits. Same per-point arithmetic either way.
+template <uint32_t D, uint32_t F, HashType H, int KIND, int MODE, bool STREAM = false>
+__device__ __forceinline__ void grid_bwd_points_regs(const uint32_t (&dyb)[STREAM ? GRID_BWD_PU : GRID_BWD_PR],
+                                                     const float (&xs0)[GRID_BWD_PU][D], const uint32_t* __restrict__ dy_lv,
                                                      uint32_t B, const float* __restrict__ pos,
                                                      uint32_t pstride, uint32_t level, const LevelInfo& li, bool hash_grid,
                                                      Interp interp, uint32_t begin, uint32_t len, uint32_t f0, uint32_t nf,
@@ -209,14 +224,25 @@ __device__ __forceinline__ void grid_bwd_points_regs(const uint32_t (&dyb)[GRID_
 	constexpr bool FAST_KIND = D == 2 && (KIND == IDX_HASH_POW2 || KIND == IDX_DENSE || KIND == IDX_HASH_RANGE);
 	const bool fast = FAST_KIND && interp == Interp::Linear && (begin == 0 || KIND == IDX_HASH_RANGE);  // whole levels or hash ranges
 	float xs[2][U][D];
+	uint32_t ds[2][STREAM ? U : 1];
 #pragma unroll
-	for (uint32_t u = 0; u < U; ++u)
+	for (uint32_t u = 0; u < U; ++u) {
 #pragma unroll
 		for (uint32_t d = 0; d < D; ++d) xs[0][u][d] = xs0[u][d];
+		if constexpr (STREAM) ds[0][u] = dyb[u];
+	}
+	// the dL/dy bits of point slot p = k U + u
+	auto dy_bits = [&](uint32_t k, uint32_t u) -> uint32_t {
+		if constexpr (STREAM) return ds[k & 1][u];
+		else return dyb[k * U + u];
+	};
 #pragma unroll
 	for (uint32_t k = 0; k < NB; ++k) {
 		if (i0 + threadIdx.x + k * U * blockDim.x >= i1) break;
-		if (k + 1 < NB) load_pos_batch<D>(pos, pstride, i0, i1, k + 1, xs[(k + 1) & 1]);
+		if (k + 1 < NB) {
+			load_pos_batch<D>(pos, pstride, i0, i1, k + 1, xs[(k + 1) & 1]);
+			if constexpr (STREAM) load_dy_batch(dy_lv, i0, i1, k + 1, ds[(k + 1) & 1]);
+		}
 		bool fast_b = fast;
 		if constexpr (FAST_KIND && KIND == IDX_DENSE) {  // dense corners below 2 size need positions in [0, 1]
 			bool inr = true;
@@ -231,10 +257,9 @@ __device__ __forceinline__ void grid_bwd_points_regs(const uint32_t (&dyb)[GRID_
 				if (i0 + threadIdx.x + (k * U + U - 1) * blockDim.x < i1) {  // the whole batch is inside the chunk
 #pragma unroll
 					for (uint32_t u = 0; u < U; ++u) {
-						const uint32_t p = k * U + u;
 						float dy[F];
 #pragma unroll
-						for (uint32_t f = 0; f < F; ++f) dy[f] = dy_bits_feature(dyb[p], f) * scale;
+						for (uint32_t f = 0; f < F; ++f) dy[f] = dy_bits_feature(dy_bits(k, u), f) * scale;
 						accum_point_2d_fast<F, H, KIND, MODE>(*(const float(*)[2]) & xs[k & 1][u][0], dy, li, f0, nf, acc, begin, len);
 					}
 				} else {
@@ -247,7 +272,7 @@ __device__ __forceinline__ void grid_bwd_points_regs(const uint32_t (&dyb)[GRID_
 						if (i0 + threadIdx.x + p * blockDim.x >= i1) break;
 						float dy[F];
 #pragma unroll
-						for (uint32_t f = 0; f < F; ++f) dy[f] = dy_bits_feature(dyb[p], f) * scale;
+						for (uint32_t f = 0; f < F; ++f) dy[f] = dy_bits_feature(dy_bits(k, u), f) * scale;
 						accum_point_2d_fast<F, H, KIND, MODE>(*(const float(*)[2]) & xs[k & 1][u][0], dy, li, f0, nf, acc, begin, len);
 					}
 				}
@@ -261,7 +286,7 @@ __device__ __forceinline__ void grid_bwd_points_regs(const uint32_t (&dyb)[GRID_
 			if (i >= i1) break;
 			float dy[F];
 #pragma unroll
-			for (uint32_t f = 0; f < F; ++f) dy[f] = dy_bits_feature(dyb[p], f) * scale;
+			for (uint32_t f = 0; f < F; ++f) dy[f] = dy_bits_feature(dy_bits(k, u), f) * scale;
 			accum_point<D, F, H, KIND, MODE, false>(xs[k & 1][u], dy, i, level, B, li, hash_grid, interp, begin, len, f0, nf, acc, o);
 		}
 	}
@@ -349,9 +374,9 @@ __device__ __forceinline__ void grid_bwd_mode_regs(int mode, const uint32_t (&dy
                                                    uint32_t begin, uint32_t len, uint32_t f0, uint32_t nf, uint32_t i0, uint32_t i1,
                                                    float scale, int* acc, const GridOpts& o) {
 	if constexpr (F == 2) {
-		if (mode == 0) { grid_bwd_points_regs<D, F, H, KIND, 0>(dyb, xs0, B, pos, pstride, level, li, hash_grid, interp, begin, len, f0, nf, i0, i1, scale, acc, o); return; }
+		if (mode == 0) { grid_bwd_points_regs<D, F, H, KIND, 0>(dyb, xs0, nullptr, B, pos, pstride, level, li, hash_grid, interp, begin, len, f0, nf, i0, i1, scale, acc, o); return; }
 	}
-	grid_bwd_points_regs<D, F, H, KIND, 1>(dyb, xs0, B, pos, pstride, level, li, hash_grid, interp, begin, len, f0, nf, i0, i1, scale, acc, o);
+	grid_bwd_points_regs<D, F, H, KIND, 1>(dyb, xs0, nullptr, B, pos, pstride, level, li, hash_grid, interp, begin, len, f0, nf, i0, i1, scale, acc, o);
 }
 
 // Network-gradient tail (extra workgroups g = 0 .. n_mlp_groups-1, on CUs the grid items leave
@@ -414,7 +439,8 @@ __global__ __launch_bounds__(GRID_BWD_THREADS) void k_grid_bwd_lds(
 	int layout, uint32_t B, const float* __restrict__ pos, uint32_t pstride, const _Float16* __restrict__ dLdy, uint32_t dy_stride,
 	const GridSlice* __restrict__ items, float* __restrict__ partial, uint32_t partial_stride,
 	const LevelInfo* __restrict__ levels, uint32_t hash_grid, uint32_t interp_u, uint32_t pts_per_chunk, uint32_t n_items,
-	uint32_t n_chunks, const GridBwdEpilogue ep, unsigned long long* dbg_times, const GridOpts o, const GridBwdTables tb) {
+	uint32_t n_chunks, const GridBwdEpilogue ep, unsigned long long* dbg_times, const GridOpts o, const GridBwdTables tb,
+	const float* __restrict__ dy_bound, uint32_t* fallback_count) {
 	extern __shared__ __attribute__((aligned(16))) int acc[];
 	const unsigned long long t_start = dbg_times ? wall_clock64() : 0ull;
 	__shared__ float red[GRID_BWD_THREADS / 64];
@@ -451,7 +477,6 @@ __global__ __launch_bounds__(GRID_BWD_THREADS) void k_grid_bwd_lds(
 	// included), so 2^e (sum + rounding) < 2^31 cannot overflow, and one outlier dL/dy costs the
 	// other entries almost no resolution (a max-based bound would lose its whole ratio to the mean).
 	// A non-finite dL/dy makes the item's gradient NaN (the reference's fp16 sums would carry it).
-	float m = 0.0f;
 	// D == 2, F <= 2 without grid options, and a chunk of at most GRID_BWD_PR points per thread (the
 	// config_hash step: 32768-point chunks): the chunk's dL/dy bits are loaded once, all of them in
 	// flight together, kept in registers for the accumulation, and the pre-pass is one load latency
@@ -461,18 +486,6 @@ __global__ __launch_bounds__(GRID_BWD_THREADS) void k_grid_bwd_lds(
 	constexpr bool REGS_OK = D == 2 && F <= 2 && !OPTS;
 	const uint32_t n_pts = i1 > i0 ? i1 - i0 : 0u;
 	const bool use_regs = REGS_OK && n_pts <= GRID_BWD_THREADS * GRID_BWD_PR;
-	uint32_t dyb[GRID_BWD_PR];
-	float xs0[GRID_BWD_PU][D];  // the accumulation's first position batch, in flight across the scale reduction
-	if constexpr (REGS_OK) {
-		if (use_regs) {
-#pragma unroll
-			for (uint32_t p = 0; p < GRID_BWD_PR; ++p) {
-				const uint32_t i = i0 + threadIdx.x + p * blockDim.x;
-				dyb[p] = i < i1 ? load_dy_bits<F>(layout, dLdy, dy_stride, it.level, B, i) : 0u;
-			}
-			load_pos_batch<D>(pos, pstride, i0, i1, 0, xs0);
-		}
-	}
 	LevelInfo li;
 	if (it.level < tb.n_levels) {
 		li.scale = tb.levels[it.level].scale;
@@ -489,10 +502,92 @@ __global__ __launch_bounds__(GRID_BWD_THREADS) void k_grid_bwd_lds(
 	const uint32_t slots = len * nf;  // int32 slots of one replica (F = 2 packed pairs: 2 per entry)
 	const uint32_t R = max(1u, min(16u, GRID_BWD_SLOTS / max(slots, 1u)));
 	const uint32_t nz = R * slots;
-	for (uint32_t j = 4 * threadIdx.x; j + 4 <= nz; j += 4 * blockDim.x) *(int4*)(acc + j) = int4{0, 0, 0, 0};  // ds_write_b128
-	for (uint32_t j = nz / 4 * 4 + threadIdx.x; j < nz; j += blockDim.x) acc[j] = 0;
-	if (dbg_times && threadIdx.x == 0) dbg_times[8 * blockIdx.x + 6] = wall_clock64();  // zeroing issued
 	int* acc_w = acc + ((threadIdx.x >> 6) % R) * slots;
+	auto zero_acc = [&] {
+		for (uint32_t j = 4 * threadIdx.x; j + 4 <= nz; j += 4 * blockDim.x) *(int4*)(acc + j) = int4{0, 0, 0, 0};  // ds_write_b128
+		for (uint32_t j = nz / 4 * 4 + threadIdx.x; j < nz; j += blockDim.x) acc[j] = 0;
+		if (dbg_times && threadIdx.x == 0) dbg_times[8 * blockIdx.x + 6] = wall_clock64();  // zeroing issued
+	};
+	// uniform per item: index kind and accumulation mode
+	auto item_kind = [&] {
+		uint64_t full = 1;
+		for (uint32_t d = 0; d < D; ++d) full = full * li.res > 0xffffffffull ? 0x100000000ull : full * li.res;
+		const bool whole = it.begin == 0 && len == li.size;
+		int kind = IDX_GENERIC;
+		if (whole && full <= li.size) kind = IDX_DENSE;
+		else if (whole && hash_grid && (li.size & (li.size - 1)) == 0) kind = IDX_HASH_POW2;
+		else if (!whole && hash_grid && (li.size & (li.size - 1)) == 0 && full > li.size) kind = IDX_HASH_RANGE;
+		return kind;
+	};
+	const int mode = nf < F ? 1 : (F == 2 ? 0 : 2);
+	const float P = (float)(i1 > i0 ? i1 - i0 : 1u);
+	int e = 0;           // the fixed-point exponent: floor(log2(lim)), grid_bwd_scale.h
+	bool finite = true;  // the chunk's sum of |dL/dy| is finite
+
+	// Streaming path (dy_bound: the fused kernel's per-slice sums of max_f |dL/dy|, [level][B / 32]):
+	// the scale comes from the chunk's <= 1024 slice sums -- one 4-byte load per thread instead of 32
+	// -- and dL/dy streams in batches under the accumulation, like the positions. The slice sums add
+	// up in another order than the exact pre-pass, so the exponent is taken from them only where
+	// grid_bwd_scale_guard proves it equal; otherwise the workgroup (uniformly) runs the exact path
+	// below from its start (it zeroes the accumulators again; no update has been issued yet).
+	// The two paths are disjoint blocks so that neither's registers live across the other.
+	constexpr bool STREAM_OK = D == 2 && F == 2 && !OPTS;
+	bool stream = false;  // workgroup-uniform
+	if constexpr (STREAM_OK) {
+		const uint32_t n_sl = n_pts / 32u;
+		if (dy_bound && layout == 0 && nf == F && use_regs && n_pts > 0 && ((i0 | i1) & 31u) == 0 && n_sl <= GRID_BWD_THREADS) {
+			float mh = threadIdx.x < n_sl ? dy_bound[(size_t)it.level * (B / 32u) + i0 / 32u + threadIdx.x] : 0.0f;
+			const uint32_t* dy_lv = (const uint32_t*)dLdy + (size_t)it.level * B;
+			uint32_t ds0[GRID_BWD_PU];  // the first batch's dL/dy bits and positions, in flight across the reduction
+			float xs0[GRID_BWD_PU][D];
+			load_dy_batch(dy_lv, i0, i1, 0, ds0);
+			load_pos_batch<D>(pos, pstride, i0, i1, 0, xs0);
+			zero_acc();
+			// the exact reduction's butterfly and wave order over the slice sums
+#pragma unroll
+			for (int o2 = 32; o2 > 0; o2 >>= 1) mh += __shfl_xor(mh, o2);
+			if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mh;
+			__syncthreads();
+			mh = red[0];
+#pragma unroll
+			for (uint32_t w = 1; w < GRID_BWD_THREADS / 64; ++w) mh += red[w];
+			stream = grid_bwd_scale_guard(mh, P, D);
+			if (stream) {
+				e = grid_bwd_scale_exp(mh, P, D);
+				const float scale = ldexpf(1.0f, e);
+				if (dbg_times && threadIdx.x == 0) dbg_times[8 * blockIdx.x + 5] = dbg_times[8 * blockIdx.x + 1] = wall_clock64();
+				const int kind = item_kind();
+				// nf == F == 2: packed pairs (MODE 0)
+				if (kind == IDX_HASH_POW2)
+					grid_bwd_points_regs<D, F, H, IDX_HASH_POW2, 0, true>(ds0, xs0, dy_lv, B, pos, pstride, it.level, li, hash_grid != 0, interp, it.begin, len, f0, nf, i0, i1, scale, acc_w, o);
+				else if (kind == IDX_HASH_RANGE)
+					grid_bwd_points_regs<D, F, H, IDX_HASH_RANGE, 0, true>(ds0, xs0, dy_lv, B, pos, pstride, it.level, li, hash_grid != 0, interp, it.begin, len, f0, nf, i0, i1, scale, acc_w, o);
+				else if (kind == IDX_DENSE)
+					grid_bwd_points_regs<D, F, H, IDX_DENSE, 0, true>(ds0, xs0, dy_lv, B, pos, pstride, it.level, li, hash_grid != 0, interp, it.begin, len, f0, nf, i0, i1, scale, acc_w, o);
+				else
+					grid_bwd_points_regs<D, F, H, IDX_GENERIC, 0, true>(ds0, xs0, dy_lv, B, pos, pstride, it.level, li, hash_grid != 0, interp, it.begin, len, f0, nf, i0, i1, scale, acc_w, o);
+			} else {  // inside the guard band, or a non-finite sum
+				if (fallback_count && threadIdx.x == 0) atomicAdd(fallback_count, 1u);
+				__syncthreads();  // red[] is rewritten by the exact reduction
+			}
+		}
+	}
+	if (!stream) {
+	// pre-pass (see above): the exact sum m
+	float m = 0.0f;
+	uint32_t dyb[GRID_BWD_PR];
+	float xs0[GRID_BWD_PU][D];  // the accumulation's first position batch, in flight across the scale reduction
+	if constexpr (REGS_OK) {
+		if (use_regs) {
+#pragma unroll
+			for (uint32_t p = 0; p < GRID_BWD_PR; ++p) {
+				const uint32_t i = i0 + threadIdx.x + p * blockDim.x;
+				dyb[p] = i < i1 ? load_dy_bits<F>(layout, dLdy, dy_stride, it.level, B, i) : 0u;
+			}
+			load_pos_batch<D>(pos, pstride, i0, i1, 0, xs0);
+		}
+	}
+	zero_acc();
 	if constexpr (REGS_OK) {
 		if (use_regs) {
 #pragma unroll
@@ -537,26 +632,11 @@ __global__ __launch_bounds__(GRID_BWD_THREADS) void k_grid_bwd_lds(
 	m = red[0];
 #pragma unroll
 	for (uint32_t w = 1; w < GRID_BWD_THREADS / 64; ++w) m += red[w];
-	const float P = (float)(i1 > i0 ? i1 - i0 : 1u);
-	const bool finite = __builtin_isfinite(m);
-	int e = 0;
-	if (m > 0.0f && finite) {
-		const float lim = (2147483647.0f - (float)(1u << D) * P) / (m * 1.01f);
-		e = ilogbf(lim);  // floor(log2(lim))
-		e = max(-126, min(e, 100));
-	}
+	finite = __builtin_isfinite(m);
+	e = grid_bwd_scale_exp(m, P, D);
 	const float scale = ldexpf(1.0f, e);
 	if (dbg_times && threadIdx.x == 0) dbg_times[8 * blockIdx.x + 1] = wall_clock64();  // zeroing + pre-pass done
-
-	// uniform per item: index kind and accumulation mode
-	uint64_t full = 1;
-	for (uint32_t d = 0; d < D; ++d) full = full * li.res > 0xffffffffull ? 0x100000000ull : full * li.res;
-	const bool whole = it.begin == 0 && len == li.size;
-	int kind = IDX_GENERIC;
-	if (whole && full <= li.size) kind = IDX_DENSE;
-	else if (whole && hash_grid && (li.size & (li.size - 1)) == 0) kind = IDX_HASH_POW2;
-	else if (!whole && hash_grid && (li.size & (li.size - 1)) == 0 && full > li.size) kind = IDX_HASH_RANGE;
-	const int mode = nf < F ? 1 : (F == 2 ? 0 : 2);
+	const int kind = item_kind();
 	if constexpr (REGS_OK) {
 		if (use_regs) {
 			if (kind == IDX_HASH_POW2)
@@ -579,6 +659,7 @@ __global__ __launch_bounds__(GRID_BWD_THREADS) void k_grid_bwd_lds(
 	else
 		grid_bwd_mode<D, F, H, IDX_GENERIC, OPTS>(mode, layout, B, pos, pstride, dLdy, dy_stride, it.level, li, hash_grid != 0, interp, it.begin, len, f0, nf, i0, i1, scale, acc_w, o);
 	}
+	}  // !stream
 	__syncthreads();
 	if (dbg_times && threadIdx.x == 0) dbg_times[8 * blockIdx.x + 2] = wall_clock64();  // accumulation done
 	if (R > 1) {  // merge the replicas into replica 0
@@ -644,6 +725,8 @@ struct GridBwdLaunch {
 	unsigned long long* dbg_times;
 	GridOpts opts;
 	GridBwdTables tb;
+	const float* dy_bound;     // the fused kernel's slice sums of max_f |dL/dy| (null: every workgroup takes the exact pre-pass)
+	uint32_t* fallback_count;  // debug: workgroups that had dy_bound but took the exact pre-pass (null: not counted)
 };
 
 template <uint32_t D, uint32_t F, HashType H>
@@ -656,10 +739,10 @@ static void grid_bwd_t(hipStream_t st, int layout, uint32_t dys, dim3 g, size_t 
 	set_dyn_lds((const void*)k_grid_bwd_lds<D, F, H, true>, (int)GRID_BWD_LDS_BYTES, done1);
 	if (gl.opts.active)
 		hipLaunchKernelGGL((k_grid_bwd_lds<D, F, H, true>), g, dim3(GRID_BWD_THREADS), lds, st, layout, B, pos, ps, dy, dys, sl, part, pstr, lv, hg, in,
-		                   ppc, gl.n_items, gl.n_chunks, gl.ep, gl.dbg_times, gl.opts, gl.tb);
+		                   ppc, gl.n_items, gl.n_chunks, gl.ep, gl.dbg_times, gl.opts, gl.tb, gl.dy_bound, gl.fallback_count);
 	else
 		hipLaunchKernelGGL((k_grid_bwd_lds<D, F, H, false>), g, dim3(GRID_BWD_THREADS), lds, st, layout, B, pos, ps, dy, dys, sl, part, pstr, lv, hg, in,
-		                   ppc, gl.n_items, gl.n_chunks, gl.ep, gl.dbg_times, gl.opts, gl.tb);
+		                   ppc, gl.n_items, gl.n_chunks, gl.ep, gl.dbg_times, gl.opts, gl.tb, gl.dy_bound, gl.fallback_count);
 }
 
 template <uint32_t D, uint32_t F>

@@ -150,7 +150,8 @@ void launch_fused_train(hipStream_t st, uint32_t W, uint32_t IN, uint32_t NH, ui
                         float* wgrad_partial, float* loss_partial, const LevelInfo* levels, bool hash_grid,
                         Interp interp, uint32_t n_blocks, const void* dout16, const void* wimage, uint32_t loss_l2 = 0, bool inrange_index = false,
                         const void* enc16 = nullptr,  // enc16: the encoding read from memory, SoA [IN][B] (no gathers)
-                        float dout_scale = 1.0f);     // dout16 is used as fp16(dout16 * dout_scale)
+                        float dout_scale = 1.0f,      // dout16 is used as fp16(dout16 * dout_scale)
+                        float* dy_bound = nullptr);   // [L][B/32] slice sums of max_f |dL/denc| (grid_bwd_lds.h); null: none
 // LDS weight image of the fused kernels, built once per parameter update.
 size_t fused_weight_image_bytes(uint32_t W, uint32_t IN, uint32_t NH);
 void launch_pack_weights(hipStream_t st, uint32_t W, uint32_t IN, uint32_t NH, const void* params16, void* image);
@@ -184,7 +185,14 @@ void launch_grid_bwd(hipStream_t st, uint32_t D, uint32_t F, HashType h, uint32_
                      uint32_t n_slices, uint32_t n_chunks, float* partial, uint32_t partial_stride,
                      const LevelInfo* levels, bool hash_grid, Interp interp, const GridBwdEpilogue* ep = nullptr,
                      const GridOpts& opts = GridOpts{}, const GridSlice* host_slices = nullptr, const LevelInfo* host_levels = nullptr,
-                     uint32_t n_levels = 0);
+                     uint32_t n_levels = 0,
+                     // dy_bound (layout 0 only): [L][B/32] slice sums of max_f |dL/dy| written by the fused kernel that
+                     // wrote dLdy16 (launch_fused_train) -- the streaming pre-pass of grid_bwd_lds.h; null: the exact one
+                     const float* dy_bound = nullptr);
+// Debug (debug_api.h): count the workgroups of every following launch_grid_bwd that were given
+// dy_bound but took the exact pre-pass; the count of the last launch (synchronises the device).
+void grid_bwd_debug_count_fallbacks(bool on);
+uint32_t grid_bwd_debug_fallbacks();
 // Binned backward, pass 1: counting-sort the updates of the binned levels by slice (GridBinArgs).
 void launch_grid_bin(hipStream_t st, uint32_t D, uint32_t F, HashType h, uint32_t B, const float* pos, uint32_t pos_stride,
                      const void* dLdy16, int dy_layout, uint32_t dy_stride, const LevelInfo* levels, bool hash_grid, Interp interp,

@@ -347,7 +347,32 @@ struct FusedTrainArgs {
 	float dout_scale;       // EXT_DOUT: dL/dy = fp16(dout * dout_scale) (the torch binding's loss scale; 1: as given)
 	const _Float16* enc;    // ENC_MEM: the encoding kept by the forward, SoA [IN][B] (no gathers)
 	unsigned long long* prof;  // diagnostic build only: per-wave phase cycle sums [waves][8]
+	// optional [L][B/32]: per (level, 32-sample slice) the fp32 sum of max_f |dL/denc| as stored -- the
+	// grid backward's fixed-point range without its pass over dLdenc (grid_bwd_lds.h); null: not emitted
+	float* dy_bound;
 };
+
+// max(|lo|, |hi|) of a stored fp16 pair as fp32, +inf if either is not finite (the grid backward's
+// pre-pass term): fp16 magnitudes order like their bit patterns, inf / NaN at or above 0x7c00
+__device__ __forceinline__ float dy_pair_bound(uint32_t w) {
+	const uint32_t m = w & 0x7fff7fffu;
+	const uint32_t b = min(max(m >> 16, m & 0xffffu), 0x7c00u);
+	return (float)__builtin_bit_cast(_Float16, (uint16_t)b);
+}
+
+// sum over the 16 lanes of a DPP row (every lane gets it): a balanced tree -- lane pairs, quads,
+// half rows, the row -- in a fixed order
+template <int CTRL>
+__device__ __forceinline__ float dpp_row_perm(float v) {
+	return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
+}
+__device__ __forceinline__ float row_sum16(float v) {
+	v += dpp_row_perm<0xB1>(v);   // quad_perm [1, 0, 3, 2]
+	v += dpp_row_perm<0x4E>(v);   // quad_perm [2, 3, 0, 1]
+	v += dpp_row_perm<0x141>(v);  // row_half_mirror
+	v += dpp_row_perm<0x140>(v);  // row_mirror
+	return v;
+}
 
 // Diagnostic timestamps (s_memtime, in its own statement with lgkmcnt(0); compiled in only for the
 // profiling instantiation, never in the measured kernel).
@@ -475,7 +500,8 @@ __device__ __forceinline__ void slice_fwd_loss(const FusedTrainArgs& a, uint32_t
 	}
 }
 
-template <int W, int IN, int NH, Act ACT, bool EXT_DOUT, bool PROF, class TargetFn, class AfterLossFn>
+// EMIT_BOUND: the instantiation can write a.dy_bound (the trainer's own steps: loss inside, encoding gathered)
+template <int W, int IN, int NH, Act ACT, bool EXT_DOUT, bool PROF, bool EMIT_BOUND, class TargetFn, class AfterLossFn>
 __device__ __forceinline__ void fused_slice(const FusedTrainArgs& a, uint32_t base, int c, int q, const h4 (&xt)[2][IN / 16],
                                             TargetFn target, AfterLossFn after_loss, const h4 (&Gext)[2], const _Float16* sW0,
                                             const _Float16* sWh, const _Float16* sWo, _Float16* bufA, _Float16* bufD,
@@ -584,10 +610,21 @@ __device__ __forceinline__ void fused_slice(const FusedTrainArgs& a, uint32_t ba
 		const h4 d1 = __builtin_convertvector(acc1, h4);
 		const uint32_t lv = 8 * u + 2 * q;  // features 16u + 4q + r -> levels lv (r=0,1), lv+1 (r=2,3)
 		const uint32_t i0 = base + c, i1 = base + 16 + c;
-		a.dLdenc[(size_t)lv * a.B + i0] = __builtin_bit_cast(uint32_t, h2{d0[0], d0[1]});
-		a.dLdenc[(size_t)(lv + 1) * a.B + i0] = __builtin_bit_cast(uint32_t, h2{d0[2], d0[3]});
-		a.dLdenc[(size_t)lv * a.B + i1] = __builtin_bit_cast(uint32_t, h2{d1[0], d1[1]});
-		a.dLdenc[(size_t)(lv + 1) * a.B + i1] = __builtin_bit_cast(uint32_t, h2{d1[2], d1[3]});
+		const uint32_t w00 = __builtin_bit_cast(uint32_t, h2{d0[0], d0[1]}), w01 = __builtin_bit_cast(uint32_t, h2{d0[2], d0[3]});
+		const uint32_t w10 = __builtin_bit_cast(uint32_t, h2{d1[0], d1[1]}), w11 = __builtin_bit_cast(uint32_t, h2{d1[2], d1[3]});
+		a.dLdenc[(size_t)lv * a.B + i0] = w00;
+		a.dLdenc[(size_t)(lv + 1) * a.B + i0] = w01;
+		a.dLdenc[(size_t)lv * a.B + i1] = w10;
+		a.dLdenc[(size_t)(lv + 1) * a.B + i1] = w11;
+		if constexpr (EMIT_BOUND) if (a.dy_bound) {  // uniform: the slice's sum of max_f |dL/denc| per level, from the stored bits
+			const float b0 = row_sum16(dy_pair_bound(w00) + dy_pair_bound(w10));
+			const float b1 = row_sum16(dy_pair_bound(w01) + dy_pair_bound(w11));
+			if (c == 0) {
+				const uint32_t ns = a.B / 32u, sl = base / 32u;
+				a.dy_bound[(size_t)lv * ns + sl] = b0;
+				a.dy_bound[(size_t)(lv + 1) * ns + sl] = b1;
+			}
+		}
 	}
 	if constexpr (PROF) { t1 = stamp(); ph[5] += t1 - t0; t0 = t1; }
 }
@@ -901,7 +938,7 @@ __global__ __launch_bounds__(64 * FUSED_WAVES, 8 / FUSED_WAVES) void k_fused_tra
 		if constexpr (PROF) { t1 = stamp(); ph[0] += t1 - t0; t0 = t1; }
 		auto target = [&](int tau, int r, uint32_t o) { return r == 0 ? tg[tau] : a.target[(size_t)(base + 16 * tau + c) * a.dims + o]; };
 		auto after_loss = [] {};
-		fused_slice<W, IN, NH, ACT, EXT_DOUT, PROF>(a, base, c, q, xt, target, after_loss, Gext, smem + L::oW0,
+		fused_slice<W, IN, NH, ACT, EXT_DOUT, PROF, !EXT_DOUT && !ENC_MEM && !PROF>(a, base, c, q, xt, target, after_loss, Gext, smem + L::oW0,
 		                                            smem + L::oWh, smem + L::oWo, bufA, bufD, acc, ph, t0);
 	}
 	if (image_pending) {  // a wave without a slice (B % 128 != 0) still meets that barrier, its copies landed

@@ -107,6 +107,7 @@ EngineSwitches EngineSwitches::from_env() {
 		if (std::atoi(e) > 0) s.grid_bwd_chunks = (uint32_t)std::atoi(e);
 	if (const char* e = std::getenv("TCNN_GRID_BWD_RANGES"))
 		if (std::atoi(e) > 0) s.grid_bwd_ranges = (uint32_t)std::atoi(e);
+	if (const char* e = std::getenv("TCNN_GRID_BWD_STREAM")) s.no_grid_bwd_stream = std::string(e) == "0";
 	if (const char* e = std::getenv("TCNN_GRID_BWD_PLAN")) s.grid_bwd_plan = std::string(e) == "feature" ? 1 : (std::string(e) == "range" ? 0 : -1);
 	return s;
 }
@@ -332,7 +333,7 @@ GridBinArgs GridEncodingHost::bin_args(GridBwdBufs& w, uint32_t B) const {
 }
 
 void GridEncodingHost::backward_items(hipStream_t st, GridBwdBufs& w, uint32_t B, const float* pos, uint32_t pstride, const void* dy,
-                                      int layout, uint32_t dy_stride, const GridBwdEpilogue* ep, uint32_t reserved) const {
+                                      int layout, uint32_t dy_stride, const GridBwdEpilogue* ep, uint32_t reserved, const float* dy_bound) const {
 	const uint32_t n_chunks = bwd_chunks(B, reserved);
 	w.n_chunks = n_chunks;
 	w.plan = plan_for(B, reserved);
@@ -340,7 +341,7 @@ void GridEncodingHost::backward_items(hipStream_t st, GridBwdBufs& w, uint32_t B
 	if (!pl.slices.empty()) w.partial.reserve((size_t)n_chunks * n_lds_params * 4);
 	launch_grid_bwd(st, desc.n_pos_dims, desc.n_features_per_level, desc.hash_type, B, pos, pstride, dy, layout, dy_stride,
 	                pl.d_slices.as<GridSlice>(), (uint32_t)pl.slices.size(), n_chunks, w.partial.as<float>(), n_lds_params, dev_levels(),
-	                hash_grid(), desc.interp, ep, opts(), pl.slices.data(), levels.data(), (uint32_t)levels.size());
+	                hash_grid(), desc.interp, ep, opts(), pl.slices.data(), levels.data(), (uint32_t)levels.size(), dy_bound);
 }
 
 void GridEncodingHost::backward_bin(hipStream_t st, GridBwdBufs& w, uint32_t B, const float* pos, uint32_t pstride, const void* dy,
@@ -1010,7 +1011,8 @@ void NetworkHost::pack_weights(hipStream_t st, StepWorkspace& ws, const void* pa
 }
 
 void NetworkHost::fused_kernel(hipStream_t st, StepWorkspace& ws, uint32_t B, const float* pos, const float* target, uint32_t dims,
-                               float loss_scale, const void* params16, bool pack, const void* dout16, void* out16, const void* enc_soa) {
+                               float loss_scale, const void* params16, bool pack, const void* dout16, void* out16, const void* enc_soa,
+                               bool emit_dy_bound) {
 	TCNN_CHECK(B % 32 == 0, "training: batch must be a multiple of 32");
 	const uint32_t n_mlp = mlp.n_params();
 	const uint32_t L = grid->desc.n_levels, F = grid->desc.n_features_per_level;
@@ -1019,6 +1021,10 @@ void NetworkHost::fused_kernel(hipStream_t st, StepWorkspace& ws, uint32_t B, co
 	ws.n_fused_blocks = nb;
 	ws.n_loss_partials = nb;
 	ws.dLdenc.reserve((size_t)L * F * B * 2);
+	// slice sums for the grid backward's streaming pre-pass (D == 2, F == 2: the shapes it exists for)
+	// (the kernel variants with an external dL/dy or an encoding read from memory do not emit them)
+	ws.dy_bound_live = emit_dy_bound && !sw.no_grid_bwd_stream && !dout16 && !enc_soa && grid->desc.n_pos_dims == 2 && F == 2;
+	if (ws.dy_bound_live) ws.dy_bound.reserve((size_t)L * (B / 32) * 4);
 	ws.wgrad_partial.reserve((size_t)nb * n_mlp * 4);
 	ws.loss_partial.reserve((size_t)nb * 4);
 	// without a packed image that matches params16, every workgroup builds its LDS image from the
@@ -1036,7 +1042,7 @@ void NetworkHost::fused_kernel(hipStream_t st, StepWorkspace& ws, uint32_t B, co
 	                   ws.wgrad_partial.as<float>(), ws.loss_partial.as<float>(), grid->dev_levels(), grid->hash_grid(),
 	                   grid->desc.interp, nb, dout16, use_image ? ws.wimage.p : nullptr, loss_l2,
 	                   grid->inrange_index_ok && grid->desc.interp == Interp::Linear && !sw.no_inrange_index, enc_soa,
-	                   dout16 ? ext_dout_scale : 1.0f);
+	                   dout16 ? ext_dout_scale : 1.0f, ws.dy_bound_live ? ws.dy_bound.as<float>() : nullptr);
 }
 
 void NetworkHost::grid_backward(hipStream_t st, StepWorkspace& ws, uint32_t B, const float* pos, GridBwdEpilogue* ep) {
@@ -1050,7 +1056,8 @@ void NetworkHost::grid_backward(hipStream_t st, StepWorkspace& ws, uint32_t B, c
 		ep->n_wparts = ws.n_fused_blocks;
 		ep->lpart = ws.loss_partial.as<float>();
 	}
-	grid->backward_items(st, ws.gbw, B, pos, grid->desc.n_pos_dims, ws.dLdenc.p, 0, 0, ep, ep ? ep->n_mlp_groups : 0u);
+	grid->backward_items(st, ws.gbw, B, pos, grid->desc.n_pos_dims, ws.dLdenc.p, 0, 0, ep, ep ? ep->n_mlp_groups : 0u,
+	                     ws.dy_bound_live ? ws.dy_bound.as<float>() : nullptr);
 	grid->backward_bin(st, ws.gbw, B, pos, grid->desc.n_pos_dims, ws.dLdenc.p, 0, 0);
 	if (ep && ep->apply_adam) ws.wimage_valid = true;  // the epilogue wrote the image of the updated weights
 }
@@ -1342,7 +1349,7 @@ void TrainerHost::training_step_overlapped(hipStream_t st, uint32_t B, const flo
 		m.grid->forward(st, B, input, m.grid->desc.n_pos_dims, m.enc_params(w16.p), ws.enc16.p, true, 0);
 		enc_soa = ws.enc16.p;
 	}
-	m.fused_kernel(st, ws, B, input, target, n_output_dims, loss_scale, w16.p, false, nullptr, nullptr, enc_soa);
+	m.fused_kernel(st, ws, B, input, target, n_output_dims, loss_scale, w16.p, false, nullptr, nullptr, enc_soa, true);
 	mark(st, 1);
 	if (run_optimizer) ++adam_step;
 	GridBwdEpilogue ep{};
@@ -1432,7 +1439,7 @@ std::vector<uint64_t> TrainerHost::graph_key(uint32_t B, const float* input, con
 	                           (uint64_t)(uintptr_t)w32.p, (uint64_t)(uintptr_t)w16.p, (uint64_t)(uintptr_t)g16.p,
 	                           (uint64_t)(uintptr_t)g32.p, (uint64_t)(uintptr_t)m1.p, (uint64_t)(uintptr_t)m2.p,
 	                           (uint64_t)(uintptr_t)steps.p, (uint64_t)(uintptr_t)d_loss.p, (uint64_t)(uintptr_t)d_ftable.p,
-	                           (uint64_t)(uintptr_t)ws.dLdenc.p, (uint64_t)(uintptr_t)ws.wgrad_partial.p,
+	                           (uint64_t)(uintptr_t)ws.dLdenc.p, (uint64_t)(uintptr_t)ws.dy_bound.p, (uint64_t)(uintptr_t)ws.wgrad_partial.p,
 	                           (uint64_t)(uintptr_t)ws.loss_partial.p, (uint64_t)(uintptr_t)ws.wimage.p,
 	                           (uint64_t)(uintptr_t)ws.gbw.partial.p, (uint64_t)(uintptr_t)ws.gbw.recs.p,
 	                           (uint64_t)(uintptr_t)ws.gbw.dir.p, (uint64_t)(uintptr_t)ws.gbw.dysum.p, ws.n_fused_blocks,
@@ -1595,7 +1602,7 @@ void TrainerHost::training_step_part(hipStream_t st, uint32_t B, const float* in
 		return;
 	}
 	if (part == 0) {
-		m.fused_kernel(st, ws, B, input, target, n_output_dims, loss_scale, w16.p, false);
+		m.fused_kernel(st, ws, B, input, target, n_output_dims, loss_scale, w16.p, false, nullptr, nullptr, nullptr, true);
 		launch_column_sums(st, ws.wgrad_partial.as<float>(), ws.n_fused_blocks, (uint32_t)n_mlp, g32.as<float>());
 		launch_sum(st, ws.loss_partial.as<float>(), ws.n_loss_partials, d_loss.as<float>());
 		last_B = B;

@@ -83,6 +83,7 @@ struct EngineSwitches {
 	uint32_t grid_bwd_chunks = 0;   // TCNN_GRID_BWD_CHUNKS: grid backward point chunks (0: automatic)
 	uint32_t grid_bwd_ranges = 0;   // TCNN_GRID_BWD_RANGES: at least this many entry ranges per hashed level (tuning)
 	int grid_bwd_plan = -1;         // TCNN_GRID_BWD_PLAN=range|feature: force one work plan (A/B; -1: by batch)
+	bool no_grid_bwd_stream = false;  // TCNN_GRID_BWD_STREAM=0: no dy_bound from the fused kernel, exact pre-pass everywhere (A/B)
 	static EngineSwitches from_env();
 };
 
@@ -164,8 +165,9 @@ struct GridEncodingHost {
 	//                   parameter order, whole grid vector) or Adam on them (adam != nullptr)
 	//   reduce_items    fixed-order slab sums of the LDS levels into grad32[0, n_lds_params)
 	// backward() = all four: the fp32 gradient of every grid parameter into grad32 [n_params].
+	// dy_bound: launch_grid_bwd's (layout 0, written by the fused kernel beside dy)
 	void backward_items(hipStream_t st, GridBwdBufs& w, uint32_t B, const float* pos, uint32_t pstride, const void* dy, int layout,
-	                    uint32_t dy_stride, const GridBwdEpilogue* ep = nullptr, uint32_t reserved = 0) const;
+	                    uint32_t dy_stride, const GridBwdEpilogue* ep = nullptr, uint32_t reserved = 0, const float* dy_bound = nullptr) const;
 	void backward_bin(hipStream_t st, GridBwdBufs& w, uint32_t B, const float* pos, uint32_t pstride, const void* dy, int layout,
 	                  uint32_t dy_stride) const;
 	void backward_acc(hipStream_t st, GridBwdBufs& w, uint32_t B, const void* dy, int layout, uint32_t dy_stride, float* grad32,
@@ -313,6 +315,10 @@ private:
 // Workspace for one fwd/bwd over a batch of B (sizes grow only).
 struct StepWorkspace {
 	DevBuf dLdenc, wgrad_partial, loss_partial, grad32_tmp, out16, enc16, wimage;
+	// the fused kernel's slice sums of max_f |dL/denc| ([L][B/32] floats) for the grid backward's
+	// streaming pre-pass; dy_bound_live: the last fused_kernel wrote them beside dLdenc
+	DevBuf dy_bound;
+	bool dy_bound_live = false;
 	GridBwdBufs gbw;
 	DevBuf acts, delta0, delta1, dout16, red_tmp;  // layer-wise engine
 	DevBuf tile_wT;  // tile engine: transposed copy of the streamed hidden matrices
@@ -384,7 +390,7 @@ struct NetworkHost {
 	// pieces of the fused engine for the trainer's overlapped step
 	void fused_kernel(hipStream_t st, StepWorkspace& ws, uint32_t B, const float* pos, const float* target, uint32_t dims,
 	                  float loss_scale, const void* params16, bool pack, const void* dout16 = nullptr, void* out16 = nullptr,
-	                  const void* enc_soa = nullptr);
+	                  const void* enc_soa = nullptr, bool emit_dy_bound = false);
 	void grid_backward(hipStream_t st, StepWorkspace& ws, uint32_t B, const float* pos, GridBwdEpilogue* ep = nullptr);
 	void pack_weights(hipStream_t st, StepWorkspace& ws, const void* params16);
 
