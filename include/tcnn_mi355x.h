@@ -180,6 +180,9 @@ int tcnn_trainer_backward(tcnn_trainer* t, void* stream, const tcnn_trainer_cont
                           float* dL_dinput, int gradient_mode);
 /* Trainer::loss(stream, ctx) (trainer.h:205-211): synchronises stream; 0 for an external-dL/dy context */
 float tcnn_trainer_context_loss(tcnn_trainer* t, void* stream, const tcnn_trainer_context* ctx);
+/* The same with a status return and the loss in *out: CrossEntropy and Variance can be negative, which
+ * the float-returning form cannot tell from its error value. */
+int tcnn_trainer_context_loss_value(tcnn_trainer* t, void* stream, const tcnn_trainer_context* ctx, float* out);
 const void* tcnn_trainer_context_output(const tcnn_trainer_context* ctx);
 const void* tcnn_trainer_context_doutput(const tcnn_trainer_context* ctx);
 void tcnn_trainer_context_destroy(tcnn_trainer_context* ctx);
@@ -232,6 +235,16 @@ int tcnn_trainer_set_dp(tcnn_trainer* t, tcnn_dp_comm* c, int sharded);
 int tcnn_trainer_dp_gather_state(tcnn_trainer* t, void* stream);
 /* Trainer::loss(stream, ctx) of the last training step (trainer.h:205-207); synchronises `stream`. */
 float tcnn_trainer_loss(tcnn_trainer* t, void* stream);
+/* The same with a status return and the loss in *out (a loss below zero is a valid CrossEntropy /
+ * Variance result, not an error). */
+int tcnn_trainer_loss_value(tcnn_trainer* t, void* stream, float* out);
+/* Loss<T>::evaluate (loss.h of the reference): any of the nine losses (L2, RelativeL2,
+ * RelativeL2Luminance, L1, RelativeL1, Mape, Smape, CrossEntropy, Variance; case-insensitive) over
+ * fp16 predictions [n x stride] (device), fp32 targets and optional data_pdf [n x dims]. Writes the
+ * loss-scaled fp16 gradients [n x stride] and, if `values` is not NULL, the fp32 per-element values
+ * [n x stride] (each already divided by n * dims); padded columns get zeros. Returns once the work has finished. */
+int tcnn_loss_evaluate(const char* otype, void* stream, uint32_t n, uint32_t stride, uint32_t dims, float loss_scale,
+                       const void* predictions16, const float* targets, float* values, void* gradients16, const float* data_pdf);
 /* Device pointer to the last step's loss sum (fp32 scalar), for graph-friendly readback. */
 const float* tcnn_trainer_loss_device(tcnn_trainer* t);
 /* network->inference(stream, input, output fp32 [n x n_out]) (object.h:147-176) */

@@ -1,13 +1,18 @@
 // tiny-cuda-nn/loss.h -- Loss<T> / create_loss<T> (reference include/tiny-cuda-nn/loss.h,
 // src/loss.cu) for the MI355X engine. The loss is evaluated inside the engine's training step
-// (fused into the MLP kernel); this object carries its configuration into the Trainer.
-// Implemented losses: RelativeL2 (losses/relative_l2.h:40-118), L2 (losses/l2.h:40-76).
+// (fused into the MLP kernel); this object carries its configuration into the Trainer, and
+// evaluate() runs the engine's stand-alone loss kernel on caller matrices.
+// Implemented losses, the reference's nine (src/loss.cu:57-65, include/tiny-cuda-nn/losses/*.h): L2,
+// RelativeL2, RelativeL2Luminance, L1, RelativeL1, Mape, Smape, CrossEntropy, Variance; any other
+// otype throws. Predictions <= 0 are not clamped (CrossEntropy / Variance then give the reference's
+// inf / NaN), and those two losses can be negative.
 #pragma once
 
 #include <algorithm>
 #include <cctype>
 
 #include "common.h"
+#include "gpu_matrix.h"
 
 namespace tcnn {
 
@@ -32,6 +37,26 @@ public:
 	json hyperparams() const { return m_config; }
 	const json& config() const { return m_config; }
 
+	// loss.h of the reference: per-element loss values (already divided by the number of target elements)
+	// and loss-scaled gradients of fp16 predictions [stride x n]; targets and data_pdf are [dims x n],
+	// values and gradients [stride x n] with zeros in the padded rows. Returns once the work has finished.
+	void evaluate(hipStream_t stream, const float loss_scale, const GPUMatrix<T>& prediction, const GPUMatrix<float>& target,
+	              GPUMatrix<float>& values, GPUMatrix<T>& gradients, const GPUMatrix<float>* data_pdf = nullptr) const {
+		if constexpr (sizeof(T) != 2) {
+			throw std::runtime_error{"Loss::evaluate: fp32 predictions are not implemented by the MI355X engine"};
+		} else {
+			const uint32_t dims = target.m(), stride = prediction.m();
+			CHECK_THROW(prediction.n() == target.n());
+			CHECK_THROW(values.m() == stride && gradients.m() == stride);
+			CHECK_THROW(values.n() == prediction.n() && gradients.n() == prediction.n());
+			CHECK_THROW(prediction.is_contiguous() && target.is_contiguous() && values.is_contiguous() && gradients.is_contiguous());
+			if (data_pdf) CHECK_THROW(data_pdf->m() == dims && data_pdf->n() == target.n() && data_pdf->is_contiguous());
+			const std::string otype = m_config.value("otype", std::string{"RelativeL2"});
+			detail::check_rc(tcnn_loss_evaluate(otype.c_str(), stream, prediction.n(), stride, dims, loss_scale, prediction.data(), target.data(),
+			                                    values.data(), gradients.data(), data_pdf ? data_pdf->data() : nullptr));
+		}
+	}
+
 private:
 	json m_config;
 };
@@ -40,8 +65,14 @@ private:
 template <typename T>
 Loss<T>* create_loss(const json& loss) {
 	const std::string otype = loss.value("otype", std::string{"RelativeL2"});
-	if (!detail::equals_case_insensitive(otype, "RelativeL2") && !detail::equals_case_insensitive(otype, "L2"))
-		throw std::runtime_error{"Loss: type '" + otype + "' is not implemented by the MI355X engine (RelativeL2, L2)"};
+	static const char* const k_otypes[] = {"L2", "RelativeL2", "RelativeL2Luminance", "L1", "RelativeL1", "Mape", "Smape", "CrossEntropy", "Variance"};
+	bool known = false;
+	std::string list;
+	for (const char* o : k_otypes) {
+		known = known || detail::equals_case_insensitive(otype, o);
+		list += (list.empty() ? "" : ", ") + std::string{o};
+	}
+	if (!known) throw std::runtime_error{"Loss: type '" + otype + "' is not implemented by the MI355X engine (" + list + ")"};
 	json c = loss;
 	c["otype"] = otype;
 	return new Loss<T>(c);

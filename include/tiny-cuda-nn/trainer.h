@@ -227,8 +227,8 @@ public:
 	// trainer.h:205-211: synchronises `stream`
 	float loss(hipStream_t stream, const ForwardContext& ctx) const {
 		if (ctx.h && ctx.owner == this) {  // a forward() context carries its own loss values
-			const float v = tcnn_trainer_context_loss(m_h, stream, ctx.h);
-			if (v < 0.0f) throw std::runtime_error{tcnn_last_error()};
+			float v = 0.0f;  // the status-returning entry: a CrossEntropy / Variance loss can be negative
+			detail::check_rc(tcnn_trainer_context_loss_value(m_h, stream, ctx.h, &v));
 			return v;
 		}
 		if (ctx.owner != this || !ctx.loss_slot) throw std::runtime_error{"Trainer::loss: the context was not made by this trainer"};

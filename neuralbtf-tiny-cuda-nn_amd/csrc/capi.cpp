@@ -575,6 +575,13 @@ float tcnn_trainer_context_loss(tcnn_trainer* t, void* stream, const tcnn_traine
 	});
 	return v;
 }
+int tcnn_trainer_context_loss_value(tcnn_trainer* t, void* stream, const tcnn_trainer_context* ctx, float* out) {
+	return guard([&] {
+		TCNN_CHECK(ctx != nullptr, "loss: null context");
+		TCNN_CHECK(out != nullptr, "loss: null result pointer");
+		*out = t->t->ctx_loss((hipStream_t)stream, *ctx->c);
+	});
+}
 const void* tcnn_trainer_context_output(const tcnn_trainer_context* ctx) { return ctx ? ctx->c->out16.p : nullptr; }
 const void* tcnn_trainer_context_doutput(const tcnn_trainer_context* ctx) { return ctx ? ctx->c->dLdy() : nullptr; }
 void tcnn_trainer_context_destroy(tcnn_trainer_context* ctx) { delete ctx; }
@@ -622,6 +629,29 @@ float tcnn_trainer_loss(tcnn_trainer* t, void* stream) {
 	float v = -1.0f;
 	if (guard([&] { v = t->t->loss((hipStream_t)stream); }) != 0) return -1.0f;
 	return v;
+}
+int tcnn_trainer_loss_value(tcnn_trainer* t, void* stream, float* out) {
+	return guard([&] {
+		TCNN_CHECK(out != nullptr, "loss: null result pointer");
+		*out = t->t->loss((hipStream_t)stream);
+	});
+}
+int tcnn_loss_evaluate(const char* otype, void* stream, uint32_t n, uint32_t stride, uint32_t dims, float loss_scale, const void* pred16,
+                       const float* target, float* values, void* grads16, const float* pdf) {
+	return guard([&] {
+		TCNN_CHECK(otype != nullptr, "loss_evaluate: null otype");
+		const int type = loss_type_from_otype(otype);
+		TCNN_CHECK(type >= 0, std::string("Loss '") + otype + "' is not implemented by the MI355X engine (" + loss_otype_list() + ")");
+		TCNN_CHECK(dims >= 1 && dims <= stride, "loss_evaluate: dims must be in [1, stride]");
+		TCNN_CHECK(pred16 && target && grads16, "loss_evaluate: null predictions, targets or gradients");
+		TCNN_CHECK((uint64_t)n * stride < (1ull << 32), "loss_evaluate: n * stride must be below 2^32");
+		if (!n) return;
+		// the per-workgroup sums are not part of this interface: scratch, freed after the kernel (hipFree waits)
+		DevBuf part;
+		part.reserve((size_t)relative_l2_n_blocks(n, stride) * sizeof(float));
+		launch_relative_l2_partial((hipStream_t)stream, n, stride, dims, loss_scale, pred16, target, grads16, part.as<float>(), (uint32_t)type, pdf,
+		                           values);
+	});
 }
 const float* tcnn_trainer_loss_device(tcnn_trainer* t) { return t->t->d_loss.as<float>(); }
 int tcnn_trainer_inference(tcnn_trainer* t, void* stream, uint32_t n, const float* in, float* out) {

@@ -13,20 +13,19 @@ namespace tcnn_amd {
 // fused train step
 // =============================================================================================
 
-// (W64 with 3 hidden layers is not here: its dW accumulators spilled 126-216 registers at 256 and
-// it trained 1.45x slower than on the tile engine, profiles/r03_engine_choice_ab.json)
-#define TCNN_FUSED_SHAPES(X) \
-	X(64, 32, 2)             \
-	X(64, 32, 1)             \
-	X(32, 32, 2)             \
-	X(32, 32, 1)
-
 bool fused_train_supported(uint32_t W, uint32_t IN, uint32_t NH, uint32_t D, uint32_t F, uint32_t OUTP, int act, HashType h) {
 	if (F != 2 || OUTP != 16 || (D != 2 && D != 3) || (act != 0 && act != 1)) return false;
 #define X(w, in, nh) if (W == w && IN == in && NH == nh) return true;
 	TCNN_FUSED_SHAPES(X)
 #undef X
 	return false;
+}
+
+// whether the fused training kernel exists for this shape with this loss inside (LossType): every shape
+// for RelativeL2 / L2 and six of the others; RelativeL2Luminance not at W64 with two hidden layers
+// (fused_loss_luminance.hip)
+bool fused_train_loss_supported(uint32_t W, uint32_t NH, uint32_t loss_type) {
+	return !(loss_type == LOSS_RELATIVE_L2_LUMINANCE && W == 64 && NH == 2);
 }
 
 size_t fused_weight_image_bytes(uint32_t W, uint32_t IN, uint32_t NH) {
@@ -125,13 +124,13 @@ void launch_fused_train(hipStream_t st, uint32_t W, uint32_t IN, uint32_t NH, ui
                         uint32_t B, uint32_t dims, float loss_scale, const void* params16, const void* table16,
                         const float* pos, const float* target, void* out16, void* dLdenc_pairs,
                         float* wgrad_partial, float* loss_partial, const LevelInfo* levels, bool hash_grid,
-                        Interp interp, uint32_t n_blocks, const void* dout16, const void* wimage, uint32_t loss_l2,
+                        Interp interp, uint32_t n_blocks, const void* dout16, const void* wimage, uint32_t loss_type,
                         bool inrange_index, const void* enc16, float dout_scale, float* dy_bound) {
 	TCNN_CHECK(B % 32 == 0, "fused train: batch must be a multiple of 32");
 	TCNN_CHECK(wimage || ((uintptr_t)params16 & 15) == 0, "fused train: parameters must be 16-byte aligned");
 	FusedTrainArgs a;
 	a.enc = (const _Float16*)enc16;
-	a.loss_l2 = loss_l2;
+	a.loss_type = loss_type;
 	a.inrange_index = inrange_index ? 1u : 0u;
 	a.wimage = (const _Float16*)wimage;
 	a.dout = (const _Float16*)dout16;
@@ -154,6 +153,24 @@ void launch_fused_train(hipStream_t st, uint32_t W, uint32_t IN, uint32_t NH, ui
 	a.prof = nullptr;
 	TCNN_CHECK(!dy_bound || (!dout16 && !enc16), "fused train: slice sums only with the loss inside and the encoding gathered");
 	a.dy_bound = dy_bound;
+	if (!dout16 && loss_type > LOSS_L2) {
+		// the seven other losses: one kernel symbol per loss (k_fused_train_grid_loss, fused_loss_*.hip), the
+		// loss inside and the encoding gathered
+		TCNN_CHECK(!enc16, "fused train: a loss other than RelativeL2 / L2 with a kept encoding is not instantiated");
+		bool ok = false;
+		switch (loss_type) {
+			case LOSS_RELATIVE_L2_LUMINANCE: ok = launch_fused_train_loss<LOSS_RELATIVE_L2_LUMINANCE>(st, W, IN, NH, D, h, act, a, n_blocks); break;
+			case LOSS_L1: ok = launch_fused_train_loss<LOSS_L1>(st, W, IN, NH, D, h, act, a, n_blocks); break;
+			case LOSS_RELATIVE_L1: ok = launch_fused_train_loss<LOSS_RELATIVE_L1>(st, W, IN, NH, D, h, act, a, n_blocks); break;
+			case LOSS_MAPE: ok = launch_fused_train_loss<LOSS_MAPE>(st, W, IN, NH, D, h, act, a, n_blocks); break;
+			case LOSS_SMAPE: ok = launch_fused_train_loss<LOSS_SMAPE>(st, W, IN, NH, D, h, act, a, n_blocks); break;
+			case LOSS_CROSS_ENTROPY: ok = launch_fused_train_loss<LOSS_CROSS_ENTROPY>(st, W, IN, NH, D, h, act, a, n_blocks); break;
+			case LOSS_VARIANCE: ok = launch_fused_train_loss<LOSS_VARIANCE>(st, W, IN, NH, D, h, act, a, n_blocks); break;
+			default: throw std::runtime_error("fused train: unknown loss type");
+		}
+		TCNN_CHECK(ok, "fused train: unsupported shape");
+		return;
+	}
 #define X(w, in, nh) if (W == w && IN == in && NH == nh) { launch_fused_shape<w, in, nh>(st, D, h, act, a, n_blocks); return; }
 	TCNN_FUSED_SHAPES(X)
 #undef X

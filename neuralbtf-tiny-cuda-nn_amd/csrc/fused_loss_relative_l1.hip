@@ -1,0 +1,3 @@
+// fused training kernels with the LOSS_RELATIVE_L1 loss inside (see fused_loss_tu.h)
+#define TCNN_FUSED_LOSS LOSS_RELATIVE_L1
+#include "fused_loss_tu.h"

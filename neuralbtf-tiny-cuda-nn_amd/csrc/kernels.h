@@ -137,6 +137,7 @@ struct GridBwdEpilogue {
 	GradFinalize fin;        // apply_adam == 0: network gradients finalised into fin.out instead of buf.g32
 };
 
+bool fused_train_loss_supported(uint32_t W, uint32_t NH, uint32_t loss_type);  // loss_type: LossType (loss_device.h)
 // Fused train step (grid encoding -> MLP fwd -> RelativeL2 -> MLP bwd -> dW partials, dL/denc).
 // With dout16 != NULL the loss is skipped and dL/d(output) fp16 [B][16] is read instead (Module::backward).
 // Returns false if no fused kernel exists for this shape.
@@ -148,7 +149,7 @@ void launch_fused_train(hipStream_t st, uint32_t W, uint32_t IN, uint32_t NH, ui
                         uint32_t B, uint32_t dims, float loss_scale, const void* params16, const void* table16,
                         const float* pos, const float* target, void* out16, void* dLdenc_pairs,
                         float* wgrad_partial, float* loss_partial, const LevelInfo* levels, bool hash_grid,
-                        Interp interp, uint32_t n_blocks, const void* dout16, const void* wimage, uint32_t loss_l2 = 0, bool inrange_index = false,
+                        Interp interp, uint32_t n_blocks, const void* dout16, const void* wimage, uint32_t loss_type = 0, bool inrange_index = false,
                         const void* enc16 = nullptr,  // enc16: the encoding read from memory, SoA [IN][B] (no gathers)
                         float dout_scale = 1.0f,      // dout16 is used as fp16(dout16 * dout_scale)
                         float* dy_bound = nullptr);   // [L][B/32] slice sums of max_f |dL/denc| (grid_bwd_lds.h); null: none
@@ -265,7 +266,7 @@ struct TileGridEnc {
 // IN 32 = 16 levels x 2 features, 64-sample tiles; opt-in with TCNN_TILE_GENC=1, measured slower)
 bool tile_train_genc_ok(uint32_t W, uint32_t IN, uint32_t NH, int act, uint32_t B, HashType h);
 void launch_mlp_tile_train(hipStream_t st, uint32_t W, uint32_t IN, uint32_t NH, int act, int out_act, uint32_t B, uint32_t dims,
-                           float loss_scale, uint32_t loss_l2, const void* params16, const void* enc16, const float* target,
+                           float loss_scale, uint32_t loss_type, const void* params16, const void* enc16, const float* target,
                            const void* dout16, void* out16, void* dldenc, int dldenc_pairs, float* wgrad_partial, float* loss_partial,
                            void* wT, const TileGridEnc* genc = nullptr);
 // forward only (the reference's INFERENCE instantiation): enc16 fp16 [B][IN] -> out16 fp16 [B][16]
@@ -315,8 +316,8 @@ void launch_wgrad(hipStream_t st, uint32_t B, uint32_t N, uint32_t K, const void
                   uint32_t n_chunks);
 uint32_t relative_l2_n_blocks(uint32_t B, uint32_t stride);
 void launch_relative_l2_partial(hipStream_t st, uint32_t B, uint32_t stride, uint32_t dims, float loss_scale, const void* pred16,
-                                const float* target, void* grads16, float* loss_partial, uint32_t loss_l2 = 0,
-                                const float* pdf = nullptr);
+                                const float* target, void* grads16, float* loss_partial, uint32_t loss_type = 0,
+                                const float* pdf = nullptr, float* values = nullptr);  // loss_type: LossType (loss_device.h)
 // out[i] += in[i] (Accumulate-mode gradients)
 void launch_add_f32(hipStream_t st, const float* in, float* out, size_t n);
 

@@ -25,6 +25,7 @@
 #include "grid_device.h"
 #include "lds_dma.h"
 #include "kernels.h"
+#include "loss_device.h"
 
 namespace tcnn_amd {
 
@@ -330,7 +331,7 @@ struct FusedTrainArgs {
 	uint32_t dims;          // target width (n_output_dims)
 	float loss_scale;
 	float n_total;          // (float)(B * dims) as in relative_l2.h:64
-	uint32_t loss_l2;       // 0: RelativeL2 (relative_l2.h:40-76), 1: L2 (l2.h:40-76)
+	uint32_t loss_type;     // LossType (loss_device.h): 0 RelativeL2, 1 L2, ... (wave-uniform switch)
 	uint32_t inrange_index; // 1: grid_index_inrange is exact for in-range positions (Linear interpolation)
 	const _Float16* params; // MLP weights fp16 [W0 | hidden | Wout]
 	const uint32_t* table;  // grid params as half2 entries (F == 2)
@@ -413,7 +414,7 @@ struct WgradAcc {
 // base + 16 tau + c, output o (read only for o < dims); after_loss(): hook run once the targets are used.
 // Forward + loss of one 32-sample slice (shared by both fused kernels): post-activations act[j] (B
 // fragments of the next layer), dL/dy G (loss-scaled fp16, or Gext with EXT_DOUT), loss sum.
-template <int W, int IN, int NH, Act ACT, bool EXT_DOUT, bool PROF, class TargetFn>
+template <int W, int IN, int NH, Act ACT, bool EXT_DOUT, bool PROF, int LOSS, class TargetFn>
 __device__ __forceinline__ void slice_fwd_loss(const FusedTrainArgs& a, uint32_t base, int c, int q, const h4 (&xt)[2][IN / 16],
                                                TargetFn target, const h4 (&Gext)[2], const _Float16* sW0, const _Float16* sWh,
                                                const _Float16* sWo, h4 (&act)[NH][2][W / 16], h4 (&G)[2], float& loss,
@@ -481,18 +482,32 @@ __device__ __forceinline__ void slice_fwd_loss(const FusedTrainArgs& a, uint32_t
 #pragma unroll
 				for (int r = 0; r < 4; ++r) a.out[(size_t)i * 16 + 4 * r + q] = y[r];  // image row 4q + r = output 4r + q
 			}
+			// RelativeL2Luminance: the sample's luminance from lanes c, 16 + c, 32 + c (48 + c), a cross-lane
+			// read the whole wave executes (the branch is wave-uniform), before any lane drops out below
+			float lum = 0.0f;
+			if (LOSS == LOSS_RELATIVE_L2_LUMINANCE || (LOSS == LOSS_ANY && a.loss_type == LOSS_RELATIVE_L2_LUMINANCE))
+				lum = loss_luminance_xlane<true>(y, c, a.dims);
 			h4 g = zero4();
 #pragma unroll
 			for (int r = 0; r < 4; ++r) {
 				if (4u * r >= a.dims) break;  // wave-uniform: r = 0 only for <= 4 outputs
 				const uint32_t o = 4 * r + q;
 				if (o < a.dims) {
-					const float p = (float)y[r];
-					const float pse = a.loss_l2 ? 1.0f : __builtin_fmaf(p, p, 0.01f);  // L2: pdf = 1
-					const float d = p - target(tau, r, o);
-					loss += d * d / pse / a.n_total;
-					const float gr = 2.0f * d / pse;
-					g[r] = f16_rn(a.loss_scale * gr / a.n_total);
+					if constexpr (LOSS == LOSS_L2_FAMILY) {
+						// the default kernels' loss, kept as it always was (loss_eval<false, LOSS_L2_FAMILY> term for term)
+						const float p = (float)y[r];
+						const float pse = a.loss_type ? 1.0f : __builtin_fmaf(p, p, 0.01f);  // L2: pdf = 1
+						const float d = p - target(tau, r, o);
+						loss += d * d / pse / a.n_total;
+						const float gr = 2.0f * d / pse;
+						g[r] = f16_rn(a.loss_scale * gr / a.n_total);
+					} else {
+						float v;
+						_Float16 gr;
+						loss_eval<false, LOSS>(a.loss_type, (float)y[r], target(tau, r, o), 1.0f, a.n_total, a.loss_scale, lum, v, gr);  // loss_device.h
+						loss += v;
+						g[r] = gr;
+					}
 				}
 			}
 			G[tau] = g;
@@ -501,7 +516,7 @@ __device__ __forceinline__ void slice_fwd_loss(const FusedTrainArgs& a, uint32_t
 }
 
 // EMIT_BOUND: the instantiation can write a.dy_bound (the trainer's own steps: loss inside, encoding gathered)
-template <int W, int IN, int NH, Act ACT, bool EXT_DOUT, bool PROF, bool EMIT_BOUND, class TargetFn, class AfterLossFn>
+template <int W, int IN, int NH, Act ACT, bool EXT_DOUT, bool PROF, bool EMIT_BOUND, int LOSS, class TargetFn, class AfterLossFn>
 __device__ __forceinline__ void fused_slice(const FusedTrainArgs& a, uint32_t base, int c, int q, const h4 (&xt)[2][IN / 16],
                                             TargetFn target, AfterLossFn after_loss, const h4 (&Gext)[2], const _Float16* sW0,
                                             const _Float16* sWh, const _Float16* sWo, _Float16* bufA, _Float16* bufD,
@@ -512,7 +527,7 @@ __device__ __forceinline__ void fused_slice(const FusedTrainArgs& a, uint32_t ba
 	unsigned long long t1;
 	h4 act[NH][2][NT];
 	h4 G[2];
-	slice_fwd_loss<W, IN, NH, ACT, EXT_DOUT, PROF>(a, base, c, q, xt, target, Gext, sW0, sWh, sWo, act, G, acc.loss, ph, t0);
+	slice_fwd_loss<W, IN, NH, ACT, EXT_DOUT, PROF, LOSS>(a, base, c, q, xt, target, Gext, sW0, sWh, sWo, act, G, acc.loss, ph, t0);
 	after_loss();
 	if constexpr (PROF) { t1 = stamp(); ph[2] += t1 - t0; t0 = t1; }
 	// ---------------- backward + weight gradients ----------------
@@ -747,8 +762,10 @@ __device__ __forceinline__ void block_reduce_wgrad(WgradAcc<W, IN, NH>& acc, flo
 // slices in a grid-stride loop; the grid encoding's gathers go straight to registers.
 // ENC_MEM (Module backward after a forward that kept its encoding, cpp_api.cu:84-109): the encoded
 // input is read from a.enc instead of gathered from the table (D and H are then unused).
-template <int W, int IN, int NH, uint32_t D, HashType H, Act ACT, bool EXT_DOUT, bool ENC_MEM = false, bool PROF = false>
-__global__ __launch_bounds__(64 * FUSED_WAVES, 8 / FUSED_WAVES) void k_fused_train_grid(const FusedTrainArgs a) {
+// LOSS (loss_device.h): how the loss is selected -- the body is shared by k_fused_train_grid and
+// k_fused_train_grid_loss below.
+template <int W, int IN, int NH, uint32_t D, HashType H, Act ACT, bool EXT_DOUT, bool ENC_MEM, bool PROF, int LOSS>
+__device__ __forceinline__ void fused_train_grid_body(const FusedTrainArgs a) {
 	using L = FusedLayout<W, IN, NH>;
 	using RL = RegKernelLayout<W, IN, NH>;
 	constexpr int NTI = L::NTI, KI = L::KI;
@@ -938,7 +955,7 @@ __global__ __launch_bounds__(64 * FUSED_WAVES, 8 / FUSED_WAVES) void k_fused_tra
 		if constexpr (PROF) { t1 = stamp(); ph[0] += t1 - t0; t0 = t1; }
 		auto target = [&](int tau, int r, uint32_t o) { return r == 0 ? tg[tau] : a.target[(size_t)(base + 16 * tau + c) * a.dims + o]; };
 		auto after_loss = [] {};
-		fused_slice<W, IN, NH, ACT, EXT_DOUT, PROF, !EXT_DOUT && !ENC_MEM && !PROF>(a, base, c, q, xt, target, after_loss, Gext, smem + L::oW0,
+		fused_slice<W, IN, NH, ACT, EXT_DOUT, PROF, !EXT_DOUT && !ENC_MEM && !PROF, LOSS>(a, base, c, q, xt, target, after_loss, Gext, smem + L::oW0,
 		                                            smem + L::oWh, smem + L::oWo, bufA, bufD, acc, ph, t0);
 	}
 	if (image_pending) {  // a wave without a slice (B % 128 != 0) still meets that barrier, its copies landed
@@ -973,6 +990,36 @@ __global__ __launch_bounds__(64 * FUSED_WAVES, 8 / FUSED_WAVES) void k_fused_tra
 	}
 }
 
+// The default kernel: RelativeL2 or L2 by a.loss_type, as before the other losses existed (the W64
+// two-layer instantiations use all 256 registers: one more live value spills).
+template <int W, int IN, int NH, uint32_t D, HashType H, Act ACT, bool EXT_DOUT, bool ENC_MEM = false, bool PROF = false>
+__global__ __launch_bounds__(64 * FUSED_WAVES, 8 / FUSED_WAVES) void k_fused_train_grid(const FusedTrainArgs a) {
+	fused_train_grid_body<W, IN, NH, D, H, ACT, EXT_DOUT, ENC_MEM, PROF, LOSS_L2_FAMILY>(a);
+}
+
+// The seven other losses, one symbol per loss (LOSS: a LossType, fixed at compile time so that each
+// stays within the same register budget), the loss inside and the encoding gathered; chosen on the
+// host by launch_fused_train.
+template <int W, int IN, int NH, uint32_t D, HashType H, Act ACT, int LOSS>
+__global__ __launch_bounds__(64 * FUSED_WAVES, 8 / FUSED_WAVES) void k_fused_train_grid_loss(const FusedTrainArgs a) {
+	static_assert(LOSS > (int)LOSS_L2 && LOSS < (int)LOSS_N_TYPES, "one of the seven other losses");
+	fused_train_grid_body<W, IN, NH, D, H, ACT, false, false, false, LOSS>(a);
+}
+
+
+// (W64 with 3 hidden layers is not here: its dW accumulators spilled 126-216 registers at 256 and
+// it trained 1.45x slower than on the tile engine, profiles/r03_engine_choice_ab.json)
+#define TCNN_FUSED_SHAPES(X) \
+	X(64, 32, 2)             \
+	X(64, 32, 1)             \
+	X(32, 32, 2)             \
+	X(32, 32, 1)
+
+// launch of k_fused_train_grid_loss<..., LOSS> (defined per loss in fused_loss_*.hip through
+// fused_loss_tu.h); false if the shape is not one of TCNN_FUSED_SHAPES
+template <int LOSS>
+bool launch_fused_train_loss(hipStream_t st, uint32_t W, uint32_t IN, uint32_t NH, uint32_t D, HashType h, int act, const FusedTrainArgs& a,
+                             uint32_t n_blocks);
 
 // Forward-only pass (inference / forward context): input fp16 from memory, SoA ([IN][B], the grid
 // encoding's layout) or AoS ([B][IN]); output fp16 [B][16] (the reference's CM [16 x B]).

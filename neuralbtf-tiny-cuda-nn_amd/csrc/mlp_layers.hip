@@ -15,11 +15,12 @@
 //   k_layer_bwd<NT, KS>  dX = act'(H) . (dY W)        out tiles NT x 16 over K, contraction N <= 32 KS
 //   k_wgrad<MT, KT>      dW partial = dY^T X over a sample chunk (samples on the MFMA K axis,
 //                        staged through LDS and read back with ds_read_b64_tr_b16)
-//   k_relative_l2_partial RelativeL2 with per-workgroup loss partial sums
+//   k_relative_l2_partial any of the nine losses (loss_device.h) with per-workgroup loss partial sums
 #include "kernels.h"
 
 #include <type_traits>
 
+#include "loss_device.h"
 #include "mlp_fused.h"
 
 namespace tcnn_amd {
@@ -543,32 +544,37 @@ void launch_wgrad(hipStream_t st, uint32_t B, uint32_t N, uint32_t K, const void
 	TCNN_HIP_CHECK(hipGetLastError());
 }
 
-// RelativeL2 (losses/relative_l2.h:40-76) or L2 (losses/l2.h:40-76, l2 != 0) over pred fp16
-// [B][stride]; per-workgroup loss sums.
-__global__ __launch_bounds__(256) void k_relative_l2_partial(uint32_t l2, uint32_t n_elements, uint32_t stride, uint32_t dims, float loss_scale,
+// Any of the nine losses (loss_device.h) over pred fp16 [B][stride]: loss-scaled fp16 gradients,
+// optional per-element values, per-workgroup loss sums. Padded columns get zero gradients / values.
+template <bool PDF>
+__global__ __launch_bounds__(256) void k_relative_l2_partial(uint32_t type, uint32_t n_elements, uint32_t stride, uint32_t dims, float loss_scale,
                                                               float n_total, const _Float16* __restrict__ pred,
                                                               const float* __restrict__ target, _Float16* __restrict__ grads,
-                                                              float* __restrict__ loss_partial, const float* __restrict__ pdf) {
+                                                              float* __restrict__ loss_partial, const float* __restrict__ pdf,
+                                                              float* __restrict__ values) {
 	__shared__ float part[4];
 	float s = 0.0f;
 	for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n_elements; i += gridDim.x * 256) {
 		const uint32_t intra = i % stride, inter = i / stride;
 		if (intra >= dims) {
 			grads[i] = (_Float16)0.0f;
+			if (values) values[i] = 0.0f;
 			continue;
 		}
-		const float p = (float)pred[i];
-		const float pse = l2 ? 1.0f : __builtin_fmaf(p, p, 0.01f);
-		const float d = p - target[inter * dims + intra];
-		if (pdf) {  // data_pdf (relative_l2.h:64-72, l2.h:63-71): values and gradient divided by the pdf
-			const float f = pdf[inter * dims + intra];
-			s += d * d / pse / f / n_total;
-			grads[i] = f16_rn(loss_scale * (2.0f * d / pse / f) / n_total);
-			continue;
+		float lum = 0.0f;
+		if (type == LOSS_RELATIVE_L2_LUMINANCE) {  // relative_l2_luminance.h:68-77 (dims < 3: the padded columns)
+			const _Float16* row = pred + (i - intra);
+			float r = (float)row[0], g = (float)row[1], b = (float)row[2];
+			if (dims >= 6) r += (float)row[3], g += (float)row[4], b += (float)row[5];
+			lum = loss_luminance(r, g, b);
 		}
-		s += d * d / pse / n_total;
-		const float gr = 2.0f * d / pse;
-		grads[i] = f16_rn(loss_scale * gr / n_total);
+		const uint32_t ti = inter * dims + intra;
+		float v;
+		_Float16 gr;
+		loss_eval<PDF>(type, (float)pred[i], target[ti], PDF ? pdf[ti] : 1.0f, n_total, loss_scale, lum, v, gr);
+		s += v;
+		grads[i] = gr;
+		if (values) values[i] = v;
 	}
 #pragma unroll
 	for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
@@ -580,11 +586,20 @@ __global__ __launch_bounds__(256) void k_relative_l2_partial(uint32_t l2, uint32
 uint32_t relative_l2_n_blocks(uint32_t B, uint32_t stride) { return std::max(1u, std::min(div_round_up((uint64_t)B * stride, 256), 1024u)); }
 
 void launch_relative_l2_partial(hipStream_t st, uint32_t B, uint32_t stride, uint32_t dims, float loss_scale, const void* pred16,
-                                const float* target, void* grads16, float* loss_partial, uint32_t loss_l2, const float* pdf) {
+                                const float* target, void* grads16, float* loss_partial, uint32_t loss_type, const float* pdf,
+                                float* values) {
 	const uint32_t n = B * stride;
 	if (!n) return;
-	hipLaunchKernelGGL(k_relative_l2_partial, dim3(relative_l2_n_blocks(B, stride)), dim3(256), 0, st, loss_l2, n, stride, dims, loss_scale,
-	                   (float)((uint64_t)B * dims), (const _Float16*)pred16, target, (_Float16*)grads16, loss_partial, pdf);
+	TCNN_CHECK(loss_type < LOSS_N_TYPES, "loss: unknown loss type " + std::to_string(loss_type));
+	TCNN_CHECK(loss_type != LOSS_RELATIVE_L2_LUMINANCE || stride >= 6, "RelativeL2Luminance reads 6 columns of the padded output row");
+	const dim3 grid(relative_l2_n_blocks(B, stride));
+	const float n_total = (float)((uint64_t)B * dims);
+	if (pdf)
+		hipLaunchKernelGGL(k_relative_l2_partial<true>, grid, dim3(256), 0, st, loss_type, n, stride, dims, loss_scale, n_total,
+		                   (const _Float16*)pred16, target, (_Float16*)grads16, loss_partial, pdf, values);
+	else
+		hipLaunchKernelGGL(k_relative_l2_partial<false>, grid, dim3(256), 0, st, loss_type, n, stride, dims, loss_scale, n_total,
+		                   (const _Float16*)pred16, target, (_Float16*)grads16, loss_partial, pdf, values);
 	TCNN_HIP_CHECK(hipGetLastError());
 }
 

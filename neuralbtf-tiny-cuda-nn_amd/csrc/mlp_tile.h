@@ -175,7 +175,7 @@ __device__ __forceinline__ int tile_ix(int row, int col16, int col_lane) {
 	else return row * RS + col16 + col_lane;
 }
 struct TileTrainArgs {
-	uint32_t B, dims, loss_l2;
+	uint32_t B, dims, loss_type;  // loss_type: LossType (loss_device.h)
 	float loss_scale, n_total;
 	int out_act;             // output activation (ACT_*), applied after the output layer, transfer before the backward
 	const _Float16* params;  // [W0 | hidden | Wout] fp16 (unpadded width WR)
@@ -234,8 +234,11 @@ constexpr int tile_train_weu(int WR, int IN, int NH, bool RA, int TS) {
 // encode_level_f2 / _inrange, bit-identical) into slot 0. Every staging buffer is wave-local: a wave
 // waits only on its own DMA (vmcnt) before reading it back. The tile's positions arrive the same way
 // one tile ahead. Shape: 8 waves, 64-sample tiles, IN = 32 (16 levels: lane = 8 samples x 8 level pairs).
-template <int WR, int IN, int NH, Act ACT, bool RA, int TS, int GENC = 0>
-__global__ __launch_bounds__(tile_train_nthr(WR, NH, RA), tile_train_weu(WR, IN, NH, RA, TS)) void k_mlp_tile_train(const TileTrainArgs a) {
+// LOSS (loss_device.h): how the loss is selected -- the body is shared by k_mlp_tile_train (RelativeL2 / L2,
+// the code these kernels always had: several sit at their register bounds) and k_mlp_tile_train_anyloss
+// (any of the nine by a wave-uniform switch on a.loss_type; launched for the seven other losses).
+template <int WR, int IN, int NH, Act ACT, bool RA, int TS, int GENC, int LOSS>
+__device__ __forceinline__ void tile_train_body(const TileTrainArgs a) {
 	using L = TileLayout<WR, IN, NH, RA, TS>;
 	constexpr int W = L::W, NTAU = L::NTAU, KH = L::KH;
 	constexpr int MTW = L::MTW, KT0 = L::KT0, RS0 = L::RS0, RSW = L::RSW, RSG = L::RSG;
@@ -595,17 +598,30 @@ __global__ __launch_bounds__(tile_train_nthr(WR, NH, RA), tile_train_weu(WR, IN,
 			if (ext) {
 				g = __builtin_bit_cast(h4, tile_f2{tg[0], tg[1]});
 			} else {
+				// RelativeL2Luminance: cross-lane read by the whole wave (this branch and `ext` are wave-uniform)
+				float lum = 0.0f;
+				if (LOSS == LOSS_ANY && a.loss_type == LOSS_RELATIVE_L2_LUMINANCE) lum = loss_luminance_xlane<OP>(yh, c, a.dims);
 #pragma unroll
 				for (int r = 0; r < 4; ++r) {
 					if (OP && 4u * r >= a.dims) break;  // wave-uniform: r = 0 only for <= 4 outputs
 					const uint32_t o = OP ? 4 * r + q : 4 * q + r;
 					if (o < a.dims) {
-						const float p = (float)yh[r];
-						const float pse = a.loss_l2 ? 1.0f : __builtin_fmaf(p, p, 0.01f);  // relative_l2.h:67-75 / l2.h:66-74
-						const float t = (!OP || r == 0) ? tg[r] : a.target[(size_t)(base + 16 * tau + c) * a.dims + o];
-						const float d = p - t;
-						loss += d * d / pse / a.n_total;
-						g[r] = f16_rn(a.loss_scale * (2.0f * d / pse) / a.n_total);
+						if constexpr (LOSS == LOSS_L2_FAMILY) {
+							// the default kernels' loss, kept as it always was (loss_eval<false, LOSS_L2_FAMILY> term for term)
+							const float p = (float)yh[r];
+							const float pse = a.loss_type ? 1.0f : __builtin_fmaf(p, p, 0.01f);  // relative_l2.h:67-75 / l2.h:66-74
+							const float t = (!OP || r == 0) ? tg[r] : a.target[(size_t)(base + 16 * tau + c) * a.dims + o];
+							const float d = p - t;
+							loss += d * d / pse / a.n_total;
+							g[r] = f16_rn(a.loss_scale * (2.0f * d / pse) / a.n_total);
+						} else {
+							const float t = (!OP || r == 0) ? tg[r] : a.target[(size_t)(base + 16 * tau + c) * a.dims + o];
+							float v;
+							_Float16 gr;
+							loss_eval<false, LOSS>(a.loss_type, (float)yh[r], t, 1.0f, a.n_total, a.loss_scale, lum, v, gr);  // loss_device.h
+							loss += v;
+							g[r] = gr;
+						}
 					}
 				}
 			}
@@ -815,6 +831,16 @@ __global__ __launch_bounds__(tile_train_nthr(WR, NH, RA), tile_train_weu(WR, IN,
 		for (int w = 0; w < WAVES; ++w) l += wloss[w];
 		a.loss_partial[blockIdx.x] = l;
 	}
+}
+
+template <int WR, int IN, int NH, Act ACT, bool RA, int TS, int GENC = 0>
+__global__ __launch_bounds__(tile_train_nthr(WR, NH, RA), tile_train_weu(WR, IN, NH, RA, TS)) void k_mlp_tile_train(const TileTrainArgs a) {
+	tile_train_body<WR, IN, NH, ACT, RA, TS, GENC, LOSS_L2_FAMILY>(a);
+}
+
+template <int WR, int IN, int NH, Act ACT, bool RA, int TS>
+__global__ __launch_bounds__(tile_train_nthr(WR, NH, RA), tile_train_weu(WR, IN, NH, RA, TS)) void k_mlp_tile_train_anyloss(const TileTrainArgs a) {
+	tile_train_body<WR, IN, NH, ACT, RA, TS, 0, LOSS_ANY>(a);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1063,6 +1089,12 @@ inline void tile_info_fill(TileShapeInfo* info) {
 	static void tile_train_launch_v_##w(hipStream_t st, uint32_t blocks, const TileTrainArgs& a) {                               \
 		using L = TileLayout<w, IN, NH, RA, TS>;                                                                                 \
 		static uint64_t done = 0;                                                                                                \
+		static uint64_t done_any = 0;                                                                                            \
+		if (!a.dout && a.loss_type > LOSS_L2) { /* the seven other losses: their own symbol (k_mlp_tile_train_anyloss) */         \
+			set_dyn_lds((const void*)k_mlp_tile_train_anyloss<w, IN, NH, A, RA, TS>, L::BYTES, done_any);                        \
+			hipLaunchKernelGGL((k_mlp_tile_train_anyloss<w, IN, NH, A, RA, TS>), dim3(blocks), dim3(L::NTHR), L::BYTES, st, a); \
+			return;                                                                                                              \
+		}                                                                                                                        \
 		set_dyn_lds((const void*)k_mlp_tile_train<w, IN, NH, A, RA, TS>, L::BYTES, done);                                        \
 		hipLaunchKernelGGL((k_mlp_tile_train<w, IN, NH, A, RA, TS>), dim3(blocks), dim3(L::NTHR), L::BYTES, st, a);             \
 	}                                                                                                                            \

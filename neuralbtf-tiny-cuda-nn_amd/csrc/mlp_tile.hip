@@ -102,7 +102,7 @@ bool tile_train_genc_ok(uint32_t W, uint32_t IN, uint32_t NH, int act, uint32_t 
 }
 
 void launch_mlp_tile_train(hipStream_t st, uint32_t W, uint32_t IN, uint32_t NH, int act, int out_act, uint32_t B, uint32_t dims,
-                           float loss_scale, uint32_t loss_l2, const void* params16, const void* enc16, const float* target,
+                           float loss_scale, uint32_t loss_type, const void* params16, const void* enc16, const float* target,
                            const void* dout16, void* out16, void* dldenc, int dldenc_pairs, float* wgrad_partial, float* loss_partial,
                            void* wT, const TileGridEnc* genc) {
 	TCNN_CHECK(B % 32 == 0, "tile train: batch must be a multiple of 32");
@@ -112,7 +112,7 @@ void launch_mlp_tile_train(hipStream_t st, uint32_t W, uint32_t IN, uint32_t NH,
 	TileTrainArgs a{};
 	a.B = B;
 	a.dims = dims;
-	a.loss_l2 = loss_l2;
+	a.loss_type = loss_type;
 	a.loss_scale = loss_scale;
 	a.n_total = (float)((uint64_t)B * dims);
 	a.out_act = out_act;
@@ -137,6 +137,7 @@ void launch_mlp_tile_train(hipStream_t st, uint32_t W, uint32_t IN, uint32_t NH,
 	bool ok = false;
 	if (genc) {
 		TCNN_CHECK(!enc16 && tile_train_genc_ok(W, IN, NH, act, B, genc->hash), "tile train: in-kernel grid encode not available for this shape");
+		TCNN_CHECK(dout16 || loss_type <= LOSS_L2, "tile train: in-kernel grid encode is instantiated for RelativeL2 / L2 only");
 		a.gpos = genc->pos;
 		a.gtable = (const uint32_t*)genc->table16;
 		a.glevels = genc->levels;

@@ -1,5 +1,6 @@
 // runtime.cpp -- host runtime: JSON config surface, parameter init, trainer orchestration.
 #include "runtime.h"
+#include "loss_device.h"
 
 #include <algorithm>
 #include <cctype>
@@ -117,6 +118,29 @@ bool ieq(const std::string& a, const std::string& b) {
 	for (size_t i = 0; i < a.size(); ++i)
 		if (std::tolower((unsigned char)a[i]) != std::tolower((unsigned char)b[i])) return false;
 	return true;
+}
+
+// the reference's loss factory (src/loss.cu:57-65)
+static const struct { const char* name; uint32_t type; } k_loss_otypes[] = {
+	{"L2", LOSS_L2},
+	{"RelativeL2", LOSS_RELATIVE_L2},
+	{"RelativeL2Luminance", LOSS_RELATIVE_L2_LUMINANCE},
+	{"L1", LOSS_L1},
+	{"RelativeL1", LOSS_RELATIVE_L1},
+	{"Mape", LOSS_MAPE},
+	{"Smape", LOSS_SMAPE},
+	{"CrossEntropy", LOSS_CROSS_ENTROPY},
+	{"Variance", LOSS_VARIANCE},
+};
+int loss_type_from_otype(const std::string& otype) {
+	for (const auto& e : k_loss_otypes)
+		if (ieq(otype, e.name)) return (int)e.type;
+	return -1;
+}
+std::string loss_otype_list() {
+	std::string r;
+	for (const auto& e : k_loss_otypes) r += (r.empty() ? "" : ", ") + std::string(e.name);
+	return r;
 }
 
 template <typename T>
@@ -852,6 +876,7 @@ bool NetworkHost::fused_ok() const {
 	// CutlassMLP / "MLP" run on the layer-wise engine (the reference's separate GEMM-per-layer network)
 	const bool ff = ieq(mlp.otype, "FullyFusedMLP") || ieq(mlp.otype, "MegakernelMLP");
 	if (sw.no_fused_grid) return false;  // A/B switch: the tile engine instead
+	if (!fused_train_loss_supported(mlp.width, mlp.n_hidden_layers, loss_type)) return false;  // the tile engine instead
 	return ff && grid && grid->n_to_pad == 0 && !grid->opts().active && mlp.output_activation == 0 &&
 	       (mlp.activation == ACT_NONE || mlp.activation == ACT_RELU) &&
 	       fused_train_supported(mlp.width, mlp.n_input, mlp.n_hidden_layers, grid->desc.n_pos_dims,
@@ -1040,7 +1065,7 @@ void NetworkHost::fused_kernel(hipStream_t st, StepWorkspace& ws, uint32_t B, co
 	launch_fused_train(st, mlp.width, mlp.n_input, mlp.n_hidden_layers, grid->desc.n_pos_dims, grid->desc.hash_type,
 	                   mlp.activation, B, dims, loss_scale, params16, enc_params(params16), pos, target, out16, ws.dLdenc.p,
 	                   ws.wgrad_partial.as<float>(), ws.loss_partial.as<float>(), grid->dev_levels(), grid->hash_grid(),
-	                   grid->desc.interp, nb, dout16, use_image ? ws.wimage.p : nullptr, loss_l2,
+	                   grid->desc.interp, nb, dout16, use_image ? ws.wimage.p : nullptr, loss_type,
 	                   grid->inrange_index_ok && grid->desc.interp == Interp::Linear && !sw.no_inrange_index, enc_soa,
 	                   dout16 ? ext_dout_scale : 1.0f, ws.dy_bound_live ? ws.dy_bound.as<float>() : nullptr);
 }
@@ -1110,6 +1135,7 @@ void NetworkHost::fwd_bwd_tile(hipStream_t st, StepWorkspace& ws, uint32_t B, co
 	TileGridEnc genc{};
 	const bool in_kernel = !enc_aos && grid && grid->desc.n_pos_dims == 2 && grid->desc.n_features_per_level == 2 &&
 	                       grid->n_to_pad == 0 && grid->desc.interp == Interp::Linear && !grid->opts().active &&
+	                       (dout16 || loss_type <= LOSS_L2) &&  // the in-kernel encode is instantiated for the default kernel only
 	                       tile_train_genc_ok(W, IN, NH, mlp.activation, B, grid->desc.hash_type);
 	if (in_kernel) {
 		genc.pos = pos;
@@ -1131,7 +1157,7 @@ void NetworkHost::fwd_bwd_tile(hipStream_t st, StepWorkspace& ws, uint32_t B, co
 	if (enc_grad) ws.delta0.reserve((size_t)B * IN * 2);
 	const uint32_t wT_bytes = tile_train_wT_bytes(W, IN, NH);
 	if (wT_bytes) ws.tile_wT.reserve(wT_bytes);
-	launch_mlp_tile_train(st, W, IN, NH, mlp.activation, mlp.output_activation, B, dims, loss_scale, loss_l2, params16, enc_aos, target,
+	launch_mlp_tile_train(st, W, IN, NH, mlp.activation, mlp.output_activation, B, dims, loss_scale, loss_type, params16, enc_aos, target,
 	                      dout16, out16,
 	                      enc_grad ? ws.delta0.p : nullptr, dy_layout == 0 ? 1 : 0, ws.wgrad_partial.as<float>(), ws.loss_partial.as<float>(),
 	                      wT_bytes ? ws.tile_wT.p : nullptr, in_kernel ? &genc : nullptr);
@@ -1179,7 +1205,7 @@ void NetworkHost::fwd_bwd_layered(hipStream_t st, StepWorkspace& ws, uint32_t B,
 	} else {
 		const uint32_t nl = relative_l2_n_blocks(B, OUTP);
 		ws.loss_partial.reserve((size_t)nl * 4);
-		launch_relative_l2_partial(st, B, OUTP, dims, loss_scale, out, target, ws.dout16.p, ws.loss_partial.as<float>(), loss_l2);
+		launch_relative_l2_partial(st, B, OUTP, dims, loss_scale, out, target, ws.dout16.p, ws.loss_partial.as<float>(), loss_type);
 		ws.n_loss_partials = nl;
 	}
 	launch_act_bwd_inplace(st, B * OUTP, mlp.output_activation, out, ws.dout16.p);
@@ -1233,13 +1259,15 @@ TrainerHost::TrainerHost(uint32_t n_in, uint32_t n_out, const json& cfg, uint32_
 	const json opt = jhas(cfg, "optimizer") ? cfg["optimizer"] : json::object();
 	const json los = jhas(cfg, "loss") ? cfg["loss"] : json::object();
 	loss_otype = jval<std::string>(los, "otype", "RelativeL2");
-	TCNN_CHECK(ieq(loss_otype, "RelativeL2") || ieq(loss_otype, "L2"),
-	           "Loss '" + loss_otype + "' is not implemented by the MI355X engine (RelativeL2, L2)");
+	const int loss_type = loss_type_from_otype(loss_otype);
+	TCNN_CHECK(loss_type >= 0, "Loss '" + loss_otype + "' is not implemented by the MI355X engine (" + loss_otype_list() + ")");
 	const std::string oo = jval<std::string>(opt, "otype", "Adam");
 	TCNN_CHECK(ieq(oo, "Adam"), "Optimizer '" + oo + "' is not implemented by the MI355X engine yet");
 	adam.update(opt);
 	model = std::make_unique<NetworkHost>(n_in, n_out, enc, net);
-	model->loss_l2 = ieq(loss_otype, "L2") ? 1u : 0u;
+	model->loss_type = (uint32_t)loss_type;
+	TCNN_CHECK(loss_type != LOSS_RELATIVE_L2_LUMINANCE || model->mlp.padded_output >= 6,
+	           "RelativeL2Luminance reads 6 columns of the padded output row");
 	n_params = model->n_params();
 	n_mlp = model->mlp.n_params();
 	initialize_params(seed);
@@ -1676,7 +1704,7 @@ std::unique_ptr<TrainerFwdCtx> TrainerHost::forward(hipStream_t st, uint32_t B, 
 			loss_in = c->pert16.p;
 		}
 		launch_relative_l2_partial(st, B, OUTP, n_output_dims, loss_scale, loss_in, target, c->dLdy16.p, c->lpart.as<float>(),
-		                           m.loss_l2, pdf);
+		                           m.loss_type, pdf);
 	}
 	ws.wimage_valid = false;  // forward_keep may have packed the image in place
 	return c;

@@ -45,6 +45,9 @@ struct DevBuf {
 };
 
 bool ieq(const std::string& a, const std::string& b);
+// LossType (loss_device.h) of a loss otype, compared case-insensitively; -1: not one of the nine
+int loss_type_from_otype(const std::string& otype);
+std::string loss_otype_list();  // "L2, RelativeL2, ..." for error messages
 
 // Scratch of one grid backward (grow-only).
 struct GridBwdBufs {
@@ -347,7 +350,7 @@ struct NetworkHost {
 	GridEncodingHost* grid = nullptr;  // enc->lone_grid(), cached: the fused path reads it every step
 	MlpHost mlp;
 	uint32_t n_input_dims = 0, n_output_dims = 0;
-	uint32_t loss_l2 = 0;  // training loss: 0 RelativeL2 (relative_l2.h), 1 L2 (l2.h)
+	uint32_t loss_type = 0;  // training loss: LossType (loss_device.h), 0 RelativeL2, 1 L2, ...
 	NetworkHost(uint32_t n_in, uint32_t n_out, const json& enc, const json& net);
 	uint64_t n_params() const { return (uint64_t)mlp.n_params() + enc->n_params(); }
 	// the encoding's parameters inside params16 ([mlp | encoding] fp16)

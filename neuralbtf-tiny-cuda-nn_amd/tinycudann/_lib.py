@@ -62,6 +62,7 @@ _SIGS = {
     "tcnn_trainer_forward_perturbed": (c_void_p, [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
     "tcnn_trainer_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_int]),
     "tcnn_trainer_context_loss": (c_float, [c_void_p, c_void_p, c_void_p]),
+    "tcnn_trainer_context_loss_value": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "tcnn_trainer_context_output": (c_void_p, [c_void_p]),
     "tcnn_trainer_context_doutput": (c_void_p, [c_void_p]),
     "tcnn_trainer_context_destroy": (None, [c_void_p]),
@@ -73,6 +74,9 @@ _SIGS = {
     "tcnn_trainer_optimizer_step_range": (c_int, [c_void_p, c_void_p, c_uint64, c_uint64]),
     "tcnn_trainer_training_step_part": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_int]),
     "tcnn_trainer_loss": (c_float, [c_void_p, c_void_p]),
+    "tcnn_trainer_loss_value": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "tcnn_loss_evaluate": (c_int, [c_char_p, c_void_p, c_uint32, c_uint32, c_uint32, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p]),
     "tcnn_trainer_loss_device": (c_void_p, [c_void_p]),
     "tcnn_trainer_inference": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p]),
     "tcnn_trainer_n_params": (c_uint64, [c_void_p]),

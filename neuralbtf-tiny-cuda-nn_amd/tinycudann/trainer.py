@@ -84,10 +84,10 @@ class Trainer:
         L.check(L.lib().tcnn_trainer_optimizer_step_range(self.h, _stream(stream), int(begin), int(end)))
 
     def loss(self, stream=None):
-        v = L.lib().tcnn_trainer_loss(self.h, _stream(stream))
-        if v < 0:
-            raise L.TcnnError(L.lib().tcnn_last_error().decode())
-        return v
+        # the status-returning entry: CrossEntropy and Variance losses can be negative
+        v = ctypes.c_float(0.0)
+        L.check(L.lib().tcnn_trainer_loss_value(self.h, _stream(stream), ctypes.byref(v)))
+        return v.value
 
     def inference(self, input, stream=None):
         import torch
@@ -234,7 +234,6 @@ class ForwardContext:
         return self._view(L.lib().tcnn_trainer_context_doutput(self.h))
 
     def loss(self, stream=None):
-        v = L.lib().tcnn_trainer_context_loss(self.trainer.h, _stream(stream), self.h)
-        if v < 0:
-            raise L.TcnnError(L.lib().tcnn_last_error().decode())
-        return v
+        v = ctypes.c_float(0.0)
+        L.check(L.lib().tcnn_trainer_context_loss_value(self.trainer.h, _stream(stream), self.h, ctypes.byref(v)))
+        return v.value
