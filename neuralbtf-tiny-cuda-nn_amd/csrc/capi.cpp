@@ -251,15 +251,15 @@ struct ModuleEncoding : ModuleBase {
 		const uint32_t W = enc.padded_output_width();
 		if (enc.f32) {  // fp32 module: the fp32 atomics accumulate straight into dL/dparams
 			if (dL_dparams) TCNN_HIP_CHECK(hipMemsetAsync(dL_dparams, 0, (size_t)grid->n_params * 4, st));  // GradientMode::Overwrite
-			return grid->backward_backward_input_f32(st, n, in, enc.n_dims, (const float*)params, dL_ddLdin, (const float*)dL_dout, W,
-			                                         (float*)dL_dparams, (float*)dL_ddLdout, W, dL_din);
+			return grid->backward_backward_input(st, n, in, enc.n_dims, (const float*)params, dL_ddLdin, (const float*)dL_dout, W,
+			                                     (float*)dL_dparams, (float*)dL_ddLdout, W, dL_din);
 		}
 		if (dL_dparams) {
 			grad32.reserve((size_t)grid->n_params * 4);
 			TCNN_HIP_CHECK(hipMemsetAsync(grad32.p, 0, (size_t)grid->n_params * 4, st));  // GradientMode::Overwrite
 		}
-		grid->backward_backward_input(st, n, in, enc.n_dims, params, dL_ddLdin, dL_dout, W, dL_dparams ? grad32.as<float>() : nullptr,
-		                              dL_ddLdout, W, dL_din);
+		grid->backward_backward_input(st, n, in, enc.n_dims, (const _Float16*)params, dL_ddLdin, (const _Float16*)dL_dout, W,
+		                              dL_dparams ? grad32.as<float>() : nullptr, (_Float16*)dL_ddLdout, W, dL_din);
 		if (dL_dparams) launch_cast_f32_f16(st, grad32.as<float>(), dL_dparams, grid->n_params);
 	}
 	// the lone grid (nullptr: a lone OneBlob / Identity); max_level does not go through the composite kernels yet

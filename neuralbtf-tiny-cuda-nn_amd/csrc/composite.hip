@@ -215,8 +215,9 @@ static void check_table(const CompTable& t) {
 	}
 }
 
+// T: the module's precision (_Float16 / float), both instantiated below
 template <typename T>
-static void composite_fwd_t(hipStream_t st, uint32_t B, const float* x, T* out, const CompTable& t) {
+void launch_composite_fwd(hipStream_t st, uint32_t B, const float* x, T* out, const CompTable& t) {
 	if (!B || !t.fwd_work) return;
 	check_table(t);
 	// as many waves per workgroup (4, 2, 1) as keep the staging tile within 32 KiB (one wave of the widest
@@ -234,29 +235,17 @@ static void composite_fwd_t(hipStream_t st, uint32_t B, const float* x, T* out, 
 	hipLaunchKernelGGL(k_composite_fwd<T>, dim3(div_round_up(B, threads)), dim3(threads), lds, st, B, x, out, t, vec_ok);
 	TCNN_HIP_CHECK(hipGetLastError());
 }
-
-void launch_composite_fwd(hipStream_t st, uint32_t B, const float* x, void* out16, const CompTable& t) {
-	composite_fwd_t<_Float16>(st, B, x, (_Float16*)out16, t);
-}
-void launch_composite_fwd_f32(hipStream_t st, uint32_t B, const float* x, float* out32, const CompTable& t) {
-	composite_fwd_t<float>(st, B, x, out32, t);
-}
+template void launch_composite_fwd<_Float16>(hipStream_t, uint32_t, const float*, _Float16*, const CompTable&);
+template void launch_composite_fwd<float>(hipStream_t, uint32_t, const float*, float*, const CompTable&);
 
 template <typename T>
-static void composite_bwd_input_t(hipStream_t st, uint32_t B, const float* x, const T* dy, uint32_t dy_stride, float* dx, const CompTable& t) {
+void launch_composite_bwd_input(hipStream_t st, uint32_t B, const float* x, const T* dy, uint32_t dy_stride, float* dx, const CompTable& t) {
 	if (!B || !t.n_slots) return;
 	check_table(t);
 	hipLaunchKernelGGL(k_composite_bwd_input<T>, dim3(div_round_up(B, 256), t.n_slots), dim3(256), 0, st, B, x, dy, dy_stride, dx, t);
 	TCNN_HIP_CHECK(hipGetLastError());
 }
-
-void launch_composite_bwd_input(hipStream_t st, uint32_t B, const float* x, const void* dy16, uint32_t dy_stride, float* dx,
-                                const CompTable& t) {
-	composite_bwd_input_t<_Float16>(st, B, x, (const _Float16*)dy16, dy_stride, dx, t);
-}
-void launch_composite_bwd_input_f32(hipStream_t st, uint32_t B, const float* x, const float* dy32, uint32_t dy_stride, float* dx,
-                                    const CompTable& t) {
-	composite_bwd_input_t<float>(st, B, x, dy32, dy_stride, dx, t);
-}
+template void launch_composite_bwd_input<_Float16>(hipStream_t, uint32_t, const float*, const _Float16*, uint32_t, float*, const CompTable&);
+template void launch_composite_bwd_input<float>(hipStream_t, uint32_t, const float*, const float*, uint32_t, float*, const CompTable&);
 
 }  // namespace tcnn_amd

@@ -99,10 +99,11 @@ static uint32_t ilog2(uint32_t v) {
 	return r;
 }
 
-// 16-byte stores of 8 bins: rows and the output pointer must keep every 8-bin group aligned
+// The launchers are templates on the module's precision T, instantiated for _Float16 and float below
+// each. 16-byte stores of 8 bins: rows and the output pointer must keep every 8-bin group aligned
 template <typename T>
-static void oneblob_fwd_t(hipStream_t st, uint32_t B, uint32_t D, uint32_t n_bins, const float* x, uint32_t x_stride, T* out,
-                          uint32_t out_stride, uint32_t n_pad) {
+void launch_oneblob_fwd(hipStream_t st, uint32_t B, uint32_t D, uint32_t n_bins, const float* x, uint32_t x_stride, T* out,
+                        uint32_t out_stride, uint32_t n_pad) {
 	TCNN_CHECK(n_bins > 0 && (n_bins & (n_bins - 1)) == 0, "Number of bins must be a power of 2");
 	if (!B) return;
 	constexpr uint32_t CH = 16 / sizeof(T);  // elements per 16 bytes
@@ -120,33 +121,21 @@ static void oneblob_fwd_t(hipStream_t st, uint32_t B, uint32_t D, uint32_t n_bin
 	}
 	TCNN_HIP_CHECK(hipGetLastError());
 }
-
-void launch_oneblob_fwd(hipStream_t st, uint32_t B, uint32_t D, uint32_t n_bins, const float* x, uint32_t x_stride, void* out16,
-                        uint32_t out_stride, uint32_t n_pad) {
-	oneblob_fwd_t<_Float16>(st, B, D, n_bins, x, x_stride, (_Float16*)out16, out_stride, n_pad);
-}
-void launch_oneblob_fwd_f32(hipStream_t st, uint32_t B, uint32_t D, uint32_t n_bins, const float* x, uint32_t x_stride, float* out32,
-                            uint32_t out_stride, uint32_t n_pad) {
-	oneblob_fwd_t<float>(st, B, D, n_bins, x, x_stride, out32, out_stride, n_pad);
-}
+template void launch_oneblob_fwd<_Float16>(hipStream_t, uint32_t, uint32_t, uint32_t, const float*, uint32_t, _Float16*, uint32_t, uint32_t);
+template void launch_oneblob_fwd<float>(hipStream_t, uint32_t, uint32_t, uint32_t, const float*, uint32_t, float*, uint32_t, uint32_t);
 
 template <typename T>
-static void oneblob_bwd_t(hipStream_t st, uint32_t B, uint32_t D, uint32_t n_bins, const float* x, uint32_t x_stride, const T* dy,
-                          uint32_t dy_stride, float* dx, uint32_t dx_stride) {
+void launch_oneblob_bwd(hipStream_t st, uint32_t B, uint32_t D, uint32_t n_bins, const float* x, uint32_t x_stride, const T* dy,
+                        uint32_t dy_stride, float* dx, uint32_t dx_stride) {
 	if (!B) return;
 	hipLaunchKernelGGL(k_oneblob_bwd<T>, dim3(div_round_up(B * D, 256)), dim3(256), 0, st, B, D, n_bins, ilog2(n_bins), x, x_stride, dy,
 	                   dy_stride, dx, dx_stride);
 	TCNN_HIP_CHECK(hipGetLastError());
 }
-
-void launch_oneblob_bwd(hipStream_t st, uint32_t B, uint32_t D, uint32_t n_bins, const float* x, uint32_t x_stride,
-                        const void* dy16, uint32_t dy_stride, float* dx, uint32_t dx_stride) {
-	oneblob_bwd_t<_Float16>(st, B, D, n_bins, x, x_stride, (const _Float16*)dy16, dy_stride, dx, dx_stride);
-}
-void launch_oneblob_bwd_f32(hipStream_t st, uint32_t B, uint32_t D, uint32_t n_bins, const float* x, uint32_t x_stride,
-                            const float* dy32, uint32_t dy_stride, float* dx, uint32_t dx_stride) {
-	oneblob_bwd_t<float>(st, B, D, n_bins, x, x_stride, dy32, dy_stride, dx, dx_stride);
-}
+template void launch_oneblob_bwd<_Float16>(hipStream_t, uint32_t, uint32_t, uint32_t, const float*, uint32_t, const _Float16*, uint32_t,
+                                           float*, uint32_t);
+template void launch_oneblob_bwd<float>(hipStream_t, uint32_t, uint32_t, uint32_t, const float*, uint32_t, const float*, uint32_t, float*,
+                                        uint32_t);
 
 // identity (identity.h:45-66): out = x * scale + offset (nvcc contracts to one FMA), padding 1.
 template <typename T>
@@ -174,33 +163,26 @@ __global__ __launch_bounds__(256) void k_identity_bwd(uint32_t B, uint32_t D, fl
 	dx[(size_t)i * dx_stride + j] = identity_bwd_value(dy[(size_t)i * dy_stride + j], scale);
 }
 
-void launch_identity_fwd(hipStream_t st, uint32_t B, uint32_t D, float scale, float offset, const float* x, uint32_t x_stride,
-                         void* out16, uint32_t out_stride, uint32_t n_pad) {
+template <typename T>
+void launch_identity_fwd(hipStream_t st, uint32_t B, uint32_t D, float scale, float offset, const float* x, uint32_t x_stride, T* out,
+                         uint32_t out_stride, uint32_t n_pad) {
 	if (!B) return;
-	hipLaunchKernelGGL(k_identity_fwd<_Float16>, dim3(div_round_up(B * (D + n_pad), 256)), dim3(256), 0, st, B, D, scale, offset, x, x_stride,
-	                   (_Float16*)out16, out_stride, n_pad);
+	hipLaunchKernelGGL(k_identity_fwd<T>, dim3(div_round_up(B * (D + n_pad), 256)), dim3(256), 0, st, B, D, scale, offset, x, x_stride, out,
+	                   out_stride, n_pad);
 	TCNN_HIP_CHECK(hipGetLastError());
 }
-void launch_identity_fwd_f32(hipStream_t st, uint32_t B, uint32_t D, float scale, float offset, const float* x, uint32_t x_stride,
-                             float* out32, uint32_t out_stride, uint32_t n_pad) {
-	if (!B) return;
-	hipLaunchKernelGGL(k_identity_fwd<float>, dim3(div_round_up(B * (D + n_pad), 256)), dim3(256), 0, st, B, D, scale, offset, x, x_stride,
-	                   out32, out_stride, n_pad);
-	TCNN_HIP_CHECK(hipGetLastError());
-}
+template void launch_identity_fwd<_Float16>(hipStream_t, uint32_t, uint32_t, float, float, const float*, uint32_t, _Float16*, uint32_t,
+                                            uint32_t);
+template void launch_identity_fwd<float>(hipStream_t, uint32_t, uint32_t, float, float, const float*, uint32_t, float*, uint32_t, uint32_t);
 
-void launch_identity_bwd(hipStream_t st, uint32_t B, uint32_t D, float scale, const void* dy16, uint32_t dy_stride, float* dx,
+template <typename T>
+void launch_identity_bwd(hipStream_t st, uint32_t B, uint32_t D, float scale, const T* dy, uint32_t dy_stride, float* dx,
                          uint32_t dx_stride) {
 	if (!B) return;
-	hipLaunchKernelGGL(k_identity_bwd<_Float16>, dim3(div_round_up(B * D, 256)), dim3(256), 0, st, B, D, scale, (const _Float16*)dy16,
-	                   dy_stride, dx, dx_stride);
+	hipLaunchKernelGGL(k_identity_bwd<T>, dim3(div_round_up(B * D, 256)), dim3(256), 0, st, B, D, scale, dy, dy_stride, dx, dx_stride);
 	TCNN_HIP_CHECK(hipGetLastError());
 }
-void launch_identity_bwd_f32(hipStream_t st, uint32_t B, uint32_t D, float scale, const float* dy32, uint32_t dy_stride, float* dx,
-                             uint32_t dx_stride) {
-	if (!B) return;
-	hipLaunchKernelGGL(k_identity_bwd<float>, dim3(div_round_up(B * D, 256)), dim3(256), 0, st, B, D, scale, dy32, dy_stride, dx, dx_stride);
-	TCNN_HIP_CHECK(hipGetLastError());
-}
+template void launch_identity_bwd<_Float16>(hipStream_t, uint32_t, uint32_t, float, const _Float16*, uint32_t, float*, uint32_t);
+template void launch_identity_bwd<float>(hipStream_t, uint32_t, uint32_t, float, const float*, uint32_t, float*, uint32_t);
 
 }  // namespace tcnn_amd

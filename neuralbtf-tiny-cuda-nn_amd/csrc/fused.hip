@@ -6,6 +6,7 @@
 #include <cstdlib>
 
 #include "grid_device.h"
+#include "grid_dispatch.h"
 #include "mlp_fused.h"
 
 namespace tcnn_amd {
@@ -106,32 +107,32 @@ static void launch_fused_t(hipStream_t st, const FusedTrainArgs& args, uint32_t 
 
 template <int W, int IN, int NH>
 static void launch_fused_shape(hipStream_t st, uint32_t D, HashType h, int act, const FusedTrainArgs& a, uint32_t nb) {
-#define DISPATCH_H(DD, AA)                                                                                   \
-	switch (h) {                                                                                          \
-		case HashType::Prime: launch_fused_t<W, IN, NH, DD, HashType::Prime, AA>(st, a, nb); break;       \
-		case HashType::ReversedPrime: launch_fused_t<W, IN, NH, DD, HashType::ReversedPrime, AA>(st, a, nb); break; \
-		default: launch_fused_t<W, IN, NH, DD, HashType::CoherentPrime, AA>(st, a, nb); break;            \
-	}
-	if (D == 2) {
-		if (act == 1) { DISPATCH_H(2, Act::ReLU) } else { DISPATCH_H(2, Act::None) }
-	} else {
-		if (act == 1) { DISPATCH_H(3, Act::ReLU) } else { DISPATCH_H(3, Act::None) }
-	}
-#undef DISPATCH_H
+	// D in {2, 3} (fused_train_supported) x hidden activation None / ReLU x hash
+	with_grid_hash(h, [&](auto hh) {
+		constexpr HashType H = decltype(hh)::value;
+		if (D == 2) {
+			if (act == 1) launch_fused_t<W, IN, NH, 2, H, Act::ReLU>(st, a, nb);
+			else launch_fused_t<W, IN, NH, 2, H, Act::None>(st, a, nb);
+		} else {
+			if (act == 1) launch_fused_t<W, IN, NH, 3, H, Act::ReLU>(st, a, nb);
+			else launch_fused_t<W, IN, NH, 3, H, Act::None>(st, a, nb);
+		}
+	});
 }
 
-void launch_fused_train(hipStream_t st, uint32_t W, uint32_t IN, uint32_t NH, uint32_t D, HashType h, int act,
+void launch_fused_train(hipStream_t st, const GridCall& g, uint32_t W, uint32_t IN, uint32_t NH, int act,
                         uint32_t B, uint32_t dims, float loss_scale, const void* params16, const void* table16,
                         const float* pos, const float* target, void* out16, void* dLdenc_pairs,
-                        float* wgrad_partial, float* loss_partial, const LevelInfo* levels, bool hash_grid,
-                        Interp interp, uint32_t n_blocks, const void* dout16, const void* wimage, uint32_t loss_type,
-                        bool inrange_index, const void* enc16, float dout_scale, float* dy_bound) {
+                        float* wgrad_partial, float* loss_partial, uint32_t n_blocks, const void* dout16, const void* wimage,
+                        uint32_t loss_type, const void* enc16, float dout_scale, float* dy_bound) {
+	const uint32_t D = g.D;
+	const HashType h = g.hash;
 	TCNN_CHECK(B % 32 == 0, "fused train: batch must be a multiple of 32");
 	TCNN_CHECK(wimage || ((uintptr_t)params16 & 15) == 0, "fused train: parameters must be 16-byte aligned");
 	FusedTrainArgs a;
 	a.enc = (const _Float16*)enc16;
 	a.loss_type = loss_type;
-	a.inrange_index = inrange_index ? 1u : 0u;
+	a.inrange_index = g.opts.inrange_index;
 	a.wimage = (const _Float16*)wimage;
 	a.dout = (const _Float16*)dout16;
 	a.dout_scale = dout_scale;
@@ -147,9 +148,9 @@ void launch_fused_train(hipStream_t st, uint32_t W, uint32_t IN, uint32_t NH, ui
 	a.dLdenc = (uint32_t*)dLdenc_pairs;
 	a.wgrad_partial = wgrad_partial;
 	a.loss_partial = loss_partial;
-	a.levels = levels;
-	a.hash_grid = hash_grid ? 1u : 0u;
-	a.interp = (uint32_t)interp;
+	a.levels = g.levels;
+	a.hash_grid = g.hash_grid ? 1u : 0u;
+	a.interp = (uint32_t)g.interp;
 	a.prof = nullptr;
 	TCNN_CHECK(!dy_bound || (!dout16 && !enc16), "fused train: slice sums only with the loss inside and the encoding gathered");
 	a.dy_bound = dy_bound;
@@ -228,23 +229,20 @@ static void launch_fused_fwd_t(hipStream_t st, const FusedFwdArgs& a) {
 
 template <int W, int IN, int NH>
 static void launch_fused_fwd_shape(hipStream_t st, uint32_t D, HashType h, int act, const FusedFwdArgs& a) {
-#define DISPATCH_H(DD, AA)                                                                                   \
-	switch (h) {                                                                                          \
-		case HashType::Prime: launch_fused_fwd_t<W, IN, NH, DD, HashType::Prime, AA>(st, a); break;       \
-		case HashType::ReversedPrime: launch_fused_fwd_t<W, IN, NH, DD, HashType::ReversedPrime, AA>(st, a); break; \
-		default: launch_fused_fwd_t<W, IN, NH, DD, HashType::CoherentPrime, AA>(st, a); break;            \
-	}
-	if (D == 2) {
-		if (act == 1) { DISPATCH_H(2, Act::ReLU) } else { DISPATCH_H(2, Act::None) }
-	} else {
-		if (act == 1) { DISPATCH_H(3, Act::ReLU) } else { DISPATCH_H(3, Act::None) }
-	}
-#undef DISPATCH_H
+	with_grid_hash(h, [&](auto hh) {
+		constexpr HashType H = decltype(hh)::value;
+		if (D == 2) {
+			if (act == 1) launch_fused_fwd_t<W, IN, NH, 2, H, Act::ReLU>(st, a);
+			else launch_fused_fwd_t<W, IN, NH, 2, H, Act::None>(st, a);
+		} else {
+			if (act == 1) launch_fused_fwd_t<W, IN, NH, 3, H, Act::ReLU>(st, a);
+			else launch_fused_fwd_t<W, IN, NH, 3, H, Act::None>(st, a);
+		}
+	});
 }
 
-void launch_fused_fwd(hipStream_t st, uint32_t W, uint32_t IN, uint32_t NH, uint32_t D, HashType h, int act, uint32_t B,
-                      const void* wimage, const void* params16, const void* table16, const float* pos, const LevelInfo* levels, bool hash_grid,
-                      Interp interp, bool inrange_index, void* enc16, void* out16) {
+void launch_fused_fwd(hipStream_t st, const GridCall& g, uint32_t W, uint32_t IN, uint32_t NH, int act, uint32_t B,
+                      const void* wimage, const void* params16, const void* table16, const float* pos, void* enc16, void* out16) {
 	TCNN_CHECK(B % 16 == 0, "fused forward: batch must be a multiple of 16");
 	if (B == 0) return;
 	FusedFwdArgs a;
@@ -254,13 +252,13 @@ void launch_fused_fwd(hipStream_t st, uint32_t W, uint32_t IN, uint32_t NH, uint
 	a.params = (const _Float16*)params16;
 	a.table = (const uint32_t*)table16;
 	a.pos = pos;
-	a.levels = levels;
-	a.hash_grid = hash_grid ? 1u : 0u;
-	a.interp = (uint32_t)interp;
-	a.inrange_index = inrange_index ? 1u : 0u;
+	a.levels = g.levels;
+	a.hash_grid = g.hash_grid ? 1u : 0u;
+	a.interp = (uint32_t)g.interp;
+	a.inrange_index = g.opts.inrange_index;
 	a.enc = (_Float16*)enc16;
 	a.out = (_Float16*)out16;
-#define X(w, in, nh) if (W == w && IN == in && NH == nh) { launch_fused_fwd_shape<w, in, nh>(st, D, h, act, a); return; }
+#define X(w, in, nh) if (W == w && IN == in && NH == nh) { launch_fused_fwd_shape<w, in, nh>(st, g.D, g.hash, act, a); return; }
 	TCNN_FUSED_SHAPES(X)
 #undef X
 	throw std::runtime_error("fused forward: unsupported shape");

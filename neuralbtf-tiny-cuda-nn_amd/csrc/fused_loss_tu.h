@@ -4,6 +4,7 @@
 #include "kernels.h"
 
 #include "grid_device.h"
+#include "grid_dispatch.h"
 #include "mlp_fused.h"
 
 // the shapes instantiated for this loss (fused_train_loss_supported in fused.hip says the same)
@@ -24,18 +25,16 @@ static void launch_fused_loss_t(hipStream_t st, const FusedTrainArgs& args, uint
 
 template <int W, int IN, int NH>
 static void launch_fused_loss_shape(hipStream_t st, uint32_t D, HashType h, int act, const FusedTrainArgs& a, uint32_t nb) {
-#define DISPATCH_H(DD, AA)                                                                                        \
-	switch (h) {                                                                                               \
-		case HashType::Prime: launch_fused_loss_t<W, IN, NH, DD, HashType::Prime, AA>(st, a, nb); break;       \
-		case HashType::ReversedPrime: launch_fused_loss_t<W, IN, NH, DD, HashType::ReversedPrime, AA>(st, a, nb); break; \
-		default: launch_fused_loss_t<W, IN, NH, DD, HashType::CoherentPrime, AA>(st, a, nb); break;            \
-	}
-	if (D == 2) {
-		if (act == 1) { DISPATCH_H(2, Act::ReLU) } else { DISPATCH_H(2, Act::None) }
-	} else {
-		if (act == 1) { DISPATCH_H(3, Act::ReLU) } else { DISPATCH_H(3, Act::None) }
-	}
-#undef DISPATCH_H
+	with_grid_hash(h, [&](auto hh) {
+		constexpr HashType H = decltype(hh)::value;
+		if (D == 2) {
+			if (act == 1) launch_fused_loss_t<W, IN, NH, 2, H, Act::ReLU>(st, a, nb);
+			else launch_fused_loss_t<W, IN, NH, 2, H, Act::None>(st, a, nb);
+		} else {
+			if (act == 1) launch_fused_loss_t<W, IN, NH, 3, H, Act::ReLU>(st, a, nb);
+			else launch_fused_loss_t<W, IN, NH, 3, H, Act::None>(st, a, nb);
+		}
+	});
 }
 
 template <>

@@ -13,6 +13,7 @@
 #include "adam_device.h"
 #include "grid_bwd_lds.h"
 #include "grid_device.h"
+#include "grid_dispatch.h"
 
 namespace tcnn_amd {
 // =============================================================================================
@@ -224,85 +225,43 @@ __global__ __launch_bounds__(256) void k_grid_fwd_soa_f2(uint32_t B, const float
 	}
 }
 
-template <uint32_t D, uint32_t F>
-static void grid_fwd_h(hipStream_t st, HashType h, dim3 g, uint32_t B, const float* pos, uint32_t ps, const _Float16* t,
-                       _Float16* o, uint32_t soa, uint32_t os, const LevelInfo* lv, uint32_t hg, uint32_t in, const GridOpts& go) {
-	const uint32_t L = soa ? g.y : go.n_levels;
-	switch (h) {
-		case HashType::Prime: hipLaunchKernelGGL((k_grid_fwd<D, F, HashType::Prime>), g, dim3(256), 0, st, B, pos, ps, t, o, soa, os, lv, hg, in, go, L); break;
-		case HashType::ReversedPrime: hipLaunchKernelGGL((k_grid_fwd<D, F, HashType::ReversedPrime>), g, dim3(256), 0, st, B, pos, ps, t, o, soa, os, lv, hg, in, go, L); break;
-		default: hipLaunchKernelGGL((k_grid_fwd<D, F, HashType::CoherentPrime>), g, dim3(256), 0, st, B, pos, ps, t, o, soa, os, lv, hg, in, go, L); break;
-	}
-}
-
-template <uint32_t D>
-static void grid_fwd_f(hipStream_t st, uint32_t F, HashType h, dim3 g, uint32_t B, const float* pos, uint32_t ps,
-                       const _Float16* t, _Float16* o, uint32_t soa, uint32_t os, const LevelInfo* lv, uint32_t hg, uint32_t in,
-                       const GridOpts& go) {
-	switch (F) {
-		case 1: grid_fwd_h<D, 1>(st, h, g, B, pos, ps, t, o, soa, os, lv, hg, in, go); break;
-		case 2: grid_fwd_h<D, 2>(st, h, g, B, pos, ps, t, o, soa, os, lv, hg, in, go); break;
-		case 4: grid_fwd_h<D, 4>(st, h, g, B, pos, ps, t, o, soa, os, lv, hg, in, go); break;
-		case 8: grid_fwd_h<D, 8>(st, h, g, B, pos, ps, t, o, soa, os, lv, hg, in, go); break;
-		default: throw std::runtime_error("GridEncoding: n_features_per_level must be 1, 2, 4 or 8");
-	}
-}
-
-void launch_grid_fwd(hipStream_t st, uint32_t D, uint32_t F, HashType h, uint32_t B, uint32_t L,
-                     const float* pos, uint32_t pos_stride, const void* table16, void* out16, bool soa,
-                     uint32_t out_stride, const LevelInfo* levels, bool hash_grid, Interp interp, const GridOpts& go,
-                     uint32_t aos_row_cols) {
+void launch_grid_fwd(hipStream_t st, const GridCall& gc, uint32_t B, const float* pos, uint32_t pos_stride, const void* table16,
+                     void* out16, bool soa, uint32_t out_stride, uint32_t aos_row_cols) {
 	if (B == 0) return;
+	const uint32_t L = gc.L, hg = gc.hash_grid ? 1u : 0u, in = (uint32_t)gc.interp;
 	// aos_row_cols (0: the whole row): the columns of an AoS row this launch may write (even, like out_stride)
 	const uint32_t row_cols = aos_row_cols ? aos_row_cols : out_stride;
-	if (!soa && F == 2 && L <= 64 && out_stride % 2 == 0 && row_cols % 2 == 0 && interp != Interp::Nearest) {
-		const dim3 g2(div_round_up(B, 64));
-		const uint32_t* t32 = (const uint32_t*)table16;
-		_Float16* o16 = (_Float16*)out16;
-		const uint32_t hg = hash_grid ? 1u : 0u, in = (uint32_t)interp;
-#define AOS2(DD)                                                                                                                   \
-	switch (h) {                                                                                                                   \
-		case HashType::Prime: hipLaunchKernelGGL((k_grid_fwd_aos_f2<DD, HashType::Prime>), g2, dim3(256), 0, st, B, pos, pos_stride, t32, o16, out_stride, levels, hg, in, go, L, row_cols); break; \
-		case HashType::ReversedPrime: hipLaunchKernelGGL((k_grid_fwd_aos_f2<DD, HashType::ReversedPrime>), g2, dim3(256), 0, st, B, pos, pos_stride, t32, o16, out_stride, levels, hg, in, go, L, row_cols); break; \
-		default: hipLaunchKernelGGL((k_grid_fwd_aos_f2<DD, HashType::CoherentPrime>), g2, dim3(256), 0, st, B, pos, pos_stride, t32, o16, out_stride, levels, hg, in, go, L, row_cols); break; \
-	}
-		if (D == 2) { AOS2(2) }
-		else if (D == 3) { AOS2(3) }
-		else if (D == 4) { AOS2(4) }
-		else throw std::runtime_error("GridEncoding: number of input dims must be 2, 3 or 4");
-#undef AOS2
-		TCNN_HIP_CHECK(hipGetLastError());
-		return;
-	}
-	if (soa && F == 2 && interp != Interp::Nearest) {
-		const dim3 g4(div_round_up(B, 256), div_round_up(L, 4));
-		const uint32_t* t32 = (const uint32_t*)table16;
-		_Float16* o16 = (_Float16*)out16;
-		const uint32_t hg = hash_grid ? 1u : 0u, in = (uint32_t)interp;
-#define SOA2(DD)                                                                                                                   \
-	switch (h) {                                                                                                                   \
-		case HashType::Prime: hipLaunchKernelGGL((k_grid_fwd_soa_f2<DD, HashType::Prime>), g4, dim3(256), 0, st, B, pos, pos_stride, t32, o16, levels, hg, in, go, L); break; \
-		case HashType::ReversedPrime: hipLaunchKernelGGL((k_grid_fwd_soa_f2<DD, HashType::ReversedPrime>), g4, dim3(256), 0, st, B, pos, pos_stride, t32, o16, levels, hg, in, go, L); break; \
-		default: hipLaunchKernelGGL((k_grid_fwd_soa_f2<DD, HashType::CoherentPrime>), g4, dim3(256), 0, st, B, pos, pos_stride, t32, o16, levels, hg, in, go, L); break; \
-	}
-		if (D == 2) { SOA2(2) }
-		else if (D == 3) { SOA2(3) }
-		else if (D == 4) { SOA2(4) }
-		else throw std::runtime_error("GridEncoding: number of input dims must be 2, 3 or 4");
-#undef SOA2
-		TCNN_HIP_CHECK(hipGetLastError());
-		return;
-	}
-	const dim3 g = soa ? dim3(div_round_up(B, 256), L) : dim3(div_round_up(B * L, 256), 1);
-	GridOpts gol = go;
-	gol.n_levels = L;  // carries L to the AoS mapping
-	const _Float16* t = (const _Float16*)table16;
-	_Float16* o = (_Float16*)out16;
-	switch (D) {
-		case 2: grid_fwd_f<2>(st, F, h, g, B, pos, pos_stride, t, o, soa, out_stride, levels, hash_grid, (uint32_t)interp, gol); break;
-		case 3: grid_fwd_f<3>(st, F, h, g, B, pos, pos_stride, t, o, soa, out_stride, levels, hash_grid, (uint32_t)interp, gol); break;
-		case 4: grid_fwd_f<4>(st, F, h, g, B, pos, pos_stride, t, o, soa, out_stride, levels, hash_grid, (uint32_t)interp, gol); break;
-		default: throw std::runtime_error("GridEncoding: number of input dims must be 2, 3 or 4");
+	const bool f2 = gc.F == 2 && gc.interp != Interp::Nearest;  // the two F = 2 kernels
+	const uint32_t* t32 = (const uint32_t*)table16;
+	_Float16* o16 = (_Float16*)out16;
+	if (f2 && !soa && L <= 64 && out_stride % 2 == 0 && row_cols % 2 == 0) {
+		with_grid_dims(gc.D, [&](auto d) {
+			with_grid_hash(gc.hash, [&](auto h) {
+				constexpr uint32_t D = decltype(d)::value;
+				constexpr HashType H = decltype(h)::value;
+				hipLaunchKernelGGL((k_grid_fwd_aos_f2<D, H>), dim3(div_round_up(B, 64)), dim3(256), 0, st, B, pos, pos_stride, t32, o16,
+				                   out_stride, gc.levels, hg, in, gc.opts, L, row_cols);
+			});
+		});
+	} else if (f2 && soa) {
+		with_grid_dims(gc.D, [&](auto d) {
+			with_grid_hash(gc.hash, [&](auto h) {
+				constexpr uint32_t D = decltype(d)::value;
+				constexpr HashType H = decltype(h)::value;
+				hipLaunchKernelGGL((k_grid_fwd_soa_f2<D, H>), dim3(div_round_up(B, 256), div_round_up(L, 4)), dim3(256), 0, st, B, pos,
+				                   pos_stride, t32, o16, gc.levels, hg, in, gc.opts, L);
+			});
+		});
+	} else {
+		const dim3 g = soa ? dim3(div_round_up(B, 256), L) : dim3(div_round_up(B * L, 256), 1);
+		GridOpts gol = gc.opts;
+		gol.n_levels = L;  // carries L to the AoS mapping
+		with_grid_shape(gc.D, gc.F, gc.hash, [&](auto d, auto f, auto h) {
+			constexpr uint32_t D = decltype(d)::value, F = decltype(f)::value;
+			constexpr HashType H = decltype(h)::value;
+			hipLaunchKernelGGL((k_grid_fwd<D, F, H>), g, dim3(256), 0, st, B, pos, pos_stride, (const _Float16*)table16, o16, soa ? 1u : 0u,
+			                   out_stride, gc.levels, hg, in, gol, L);
+		});
 	}
 	TCNN_HIP_CHECK(hipGetLastError());
 }
@@ -414,57 +373,24 @@ __global__ __launch_bounds__(256) void k_grid_bwd_input(uint32_t B, uint32_t L, 
 	for (uint32_t d = 0; d < D; ++d) dx[(size_t)i * dx_stride + d] = res[d];
 }
 
-template <uint32_t D, uint32_t F, typename T>
-static void grid_bwd_input_h(hipStream_t st, HashType h, dim3 g, uint32_t B, uint32_t L, const float* pos, uint32_t ps, const T* t,
-                             const T* dy, int layout, uint32_t dys, float* dx, uint32_t dxs, const LevelInfo* lv, uint32_t hg,
-                             uint32_t in, const GridOpts& go) {
-	switch (h) {
-		case HashType::Prime: hipLaunchKernelGGL((k_grid_bwd_input<D, F, HashType::Prime, T>), g, dim3(256), 0, st, B, L, pos, ps, t, dy, layout, dys, dx, dxs, lv, hg, in, go); break;
-		case HashType::ReversedPrime: hipLaunchKernelGGL((k_grid_bwd_input<D, F, HashType::ReversedPrime, T>), g, dim3(256), 0, st, B, L, pos, ps, t, dy, layout, dys, dx, dxs, lv, hg, in, go); break;
-		default: hipLaunchKernelGGL((k_grid_bwd_input<D, F, HashType::CoherentPrime, T>), g, dim3(256), 0, st, B, L, pos, ps, t, dy, layout, dys, dx, dxs, lv, hg, in, go); break;
-	}
-}
-
-template <uint32_t D, typename T>
-static void grid_bwd_input_f(hipStream_t st, uint32_t F, HashType h, dim3 g, uint32_t B, uint32_t L, const float* pos, uint32_t ps,
-                             const T* t, const T* dy, int layout, uint32_t dys, float* dx, uint32_t dxs,
-                             const LevelInfo* lv, uint32_t hg, uint32_t in, const GridOpts& go) {
-	switch (F) {
-		case 1: grid_bwd_input_h<D, 1, T>(st, h, g, B, L, pos, ps, t, dy, layout, dys, dx, dxs, lv, hg, in, go); break;
-		case 2: grid_bwd_input_h<D, 2, T>(st, h, g, B, L, pos, ps, t, dy, layout, dys, dx, dxs, lv, hg, in, go); break;
-		case 4: grid_bwd_input_h<D, 4, T>(st, h, g, B, L, pos, ps, t, dy, layout, dys, dx, dxs, lv, hg, in, go); break;
-		case 8: grid_bwd_input_h<D, 8, T>(st, h, g, B, L, pos, ps, t, dy, layout, dys, dx, dxs, lv, hg, in, go); break;
-		default: throw std::runtime_error("GridEncoding: n_features_per_level must be 1, 2, 4 or 8");
-	}
-}
-
 template <typename T>
-static void grid_bwd_input_t(hipStream_t st, uint32_t D, uint32_t F, HashType h, uint32_t B, uint32_t L, const float* pos, uint32_t pos_stride,
-                             const T* t, const T* dy, int dy_layout, uint32_t dy_stride, float* dx, uint32_t dx_stride,
-                             const LevelInfo* levels, bool hash_grid, Interp interp, const GridOpts& go) {
+void launch_grid_bwd_input(hipStream_t st, const GridCall& gc, uint32_t B, const float* pos, uint32_t pos_stride, const T* table,
+                           const T* dLdy, int dy_layout, uint32_t dy_stride, float* dx, uint32_t dx_stride) {
 	if (B == 0) return;
-	const dim3 g(div_round_up(B, 256));
-	switch (D) {
-		case 2: grid_bwd_input_f<2, T>(st, F, h, g, B, L, pos, pos_stride, t, dy, dy_layout, dy_stride, dx, dx_stride, levels, hash_grid, (uint32_t)interp, go); break;
-		case 3: grid_bwd_input_f<3, T>(st, F, h, g, B, L, pos, pos_stride, t, dy, dy_layout, dy_stride, dx, dx_stride, levels, hash_grid, (uint32_t)interp, go); break;
-		case 4: grid_bwd_input_f<4, T>(st, F, h, g, B, L, pos, pos_stride, t, dy, dy_layout, dy_stride, dx, dx_stride, levels, hash_grid, (uint32_t)interp, go); break;
-		default: throw std::runtime_error("GridEncoding: number of input dims must be 2, 3 or 4");
-	}
+	const int layout = sizeof(T) == 4 ? 2 : dy_layout;  // fp32 dL/dy: AoS rows
+	with_grid_shape(gc.D, gc.F, gc.hash, [&](auto d, auto f, auto h) {
+		constexpr uint32_t D = decltype(d)::value, F = decltype(f)::value;
+		constexpr HashType H = decltype(h)::value;
+		hipLaunchKernelGGL((k_grid_bwd_input<D, F, H, T>), dim3(div_round_up(B, 256)), dim3(256), 0, st, B, gc.L, pos, pos_stride, table, dLdy,
+		                   layout, dy_stride, dx, dx_stride, gc.levels, gc.hash_grid ? 1u : 0u, (uint32_t)gc.interp, gc.opts);
+	});
 	TCNN_HIP_CHECK(hipGetLastError());
 }
+template void launch_grid_bwd_input<_Float16>(hipStream_t, const GridCall&, uint32_t, const float*, uint32_t, const _Float16*,
+                                              const _Float16*, int, uint32_t, float*, uint32_t);
+template void launch_grid_bwd_input<float>(hipStream_t, const GridCall&, uint32_t, const float*, uint32_t, const float*, const float*, int,
+                                           uint32_t, float*, uint32_t);
 
-void launch_grid_bwd_input(hipStream_t st, uint32_t D, uint32_t F, HashType h, uint32_t B, uint32_t L, const float* pos,
-                           uint32_t pos_stride, const void* table16, const void* dLdy16, int dy_layout, uint32_t dy_stride, float* dx,
-                           uint32_t dx_stride, const LevelInfo* levels, bool hash_grid, Interp interp, const GridOpts& go) {
-	grid_bwd_input_t<_Float16>(st, D, F, h, B, L, pos, pos_stride, (const _Float16*)table16, (const _Float16*)dLdy16, dy_layout, dy_stride, dx,
-	                           dx_stride, levels, hash_grid, interp, go);
-}
-
-void launch_grid_bwd_input_f32(hipStream_t st, uint32_t D, uint32_t F, HashType h, uint32_t B, uint32_t L, const float* pos,
-                               uint32_t pos_stride, const float* table32, const float* dLdy32, uint32_t dy_stride, float* dx,
-                               uint32_t dx_stride, const LevelInfo* levels, bool hash_grid, Interp interp, const GridOpts& go) {
-	grid_bwd_input_t<float>(st, D, F, h, B, L, pos, pos_stride, table32, dLdy32, 2, dy_stride, dx, dx_stride, levels, hash_grid, interp, go);
-}
 
 
 // ---------------------------------------------------------------------------------------------
@@ -580,63 +506,25 @@ __global__ __launch_bounds__(256) void k_grid_bwd_bwd(uint32_t B, uint32_t L, co
 		for (uint32_t d = 0; d < D; ++d) dx[(size_t)i * D + d] = res[d];
 }
 
-template <uint32_t D, uint32_t F, typename T>
-static void grid_bwd_bwd_h(hipStream_t st, HashType h, dim3 g, uint32_t B, uint32_t L, const float* pos, uint32_t ps,
-                           const T* t, const float* gx, const T* dy, uint32_t dys, float* grad, T* ddy,
-                           uint32_t ddys, float* dx, const LevelInfo* lv, uint32_t hg, uint32_t in, const GridOpts& go) {
-#define GBB_LAUNCH(HH) hipLaunchKernelGGL((k_grid_bwd_bwd<D, F, HH, T>), g, dim3(256), 0, st, B, L, pos, ps, t, gx, dy, dys, grad, ddy, ddys, dx, lv, hg, in, go)
-	switch (h) {
-		case HashType::Prime: GBB_LAUNCH(HashType::Prime); break;
-		case HashType::ReversedPrime: GBB_LAUNCH(HashType::ReversedPrime); break;
-		default: GBB_LAUNCH(HashType::CoherentPrime); break;
-	}
-#undef GBB_LAUNCH
-}
-
-template <uint32_t D, typename T>
-static void grid_bwd_bwd_f(hipStream_t st, uint32_t F, HashType h, dim3 g, uint32_t B, uint32_t L, const float* pos, uint32_t ps,
-                           const T* t, const float* gx, const T* dy, uint32_t dys, float* grad, T* ddy,
-                           uint32_t ddys, float* dx, const LevelInfo* lv, uint32_t hg, uint32_t in, const GridOpts& go) {
-	switch (F) {
-		case 1: grid_bwd_bwd_h<D, 1, T>(st, h, g, B, L, pos, ps, t, gx, dy, dys, grad, ddy, ddys, dx, lv, hg, in, go); break;
-		case 2: grid_bwd_bwd_h<D, 2, T>(st, h, g, B, L, pos, ps, t, gx, dy, dys, grad, ddy, ddys, dx, lv, hg, in, go); break;
-		case 4: grid_bwd_bwd_h<D, 4, T>(st, h, g, B, L, pos, ps, t, gx, dy, dys, grad, ddy, ddys, dx, lv, hg, in, go); break;
-		case 8: grid_bwd_bwd_h<D, 8, T>(st, h, g, B, L, pos, ps, t, gx, dy, dys, grad, ddy, ddys, dx, lv, hg, in, go); break;
-		default: throw std::runtime_error("GridEncoding: n_features_per_level must be 1, 2, 4 or 8");
-	}
-}
-
 template <typename T>
-static void grid_bwd_bwd_t(hipStream_t st, uint32_t D, uint32_t F, HashType h, uint32_t B, uint32_t L, const float* pos, uint32_t pos_stride,
-                           const T* t, const float* dL_ddLdx, const T* dy, uint32_t dy_stride, float* grad32, T* ddy, uint32_t ddy_stride,
-                           float* dx, const LevelInfo* levels, bool hash_grid, Interp interp, const GridOpts& go) {
+void launch_grid_bwd_bwd(hipStream_t st, const GridCall& gc, uint32_t B, const float* pos, uint32_t pos_stride, const T* table,
+                         const float* dL_ddLdx, const T* dLdy, uint32_t dy_stride, float* grad32, T* dLddLdy, uint32_t ddy_stride,
+                         float* dx) {
 	if (B == 0) return;
-	const dim3 g(div_round_up(B, 256));
-	const uint32_t hg = hash_grid ? 1u : 0u, in = (uint32_t)interp;
-	switch (D) {
-		case 2: grid_bwd_bwd_f<2, T>(st, F, h, g, B, L, pos, pos_stride, t, dL_ddLdx, dy, dy_stride, grad32, ddy, ddy_stride, dx, levels, hg, in, go); break;
-		case 3: grid_bwd_bwd_f<3, T>(st, F, h, g, B, L, pos, pos_stride, t, dL_ddLdx, dy, dy_stride, grad32, ddy, ddy_stride, dx, levels, hg, in, go); break;
-		case 4: grid_bwd_bwd_f<4, T>(st, F, h, g, B, L, pos, pos_stride, t, dL_ddLdx, dy, dy_stride, grad32, ddy, ddy_stride, dx, levels, hg, in, go); break;
-		default: throw std::runtime_error("GridEncoding: number of input dims must be 2, 3 or 4");
-	}
+	with_grid_shape(gc.D, gc.F, gc.hash, [&](auto d, auto f, auto h) {
+		constexpr uint32_t D = decltype(d)::value, F = decltype(f)::value;
+		constexpr HashType H = decltype(h)::value;
+		hipLaunchKernelGGL((k_grid_bwd_bwd<D, F, H, T>), dim3(div_round_up(B, 256)), dim3(256), 0, st, B, gc.L, pos, pos_stride, table,
+		                   dL_ddLdx, dLdy, dy_stride, grad32, dLddLdy, ddy_stride, dx, gc.levels, gc.hash_grid ? 1u : 0u,
+		                   (uint32_t)gc.interp, gc.opts);
+	});
 	TCNN_HIP_CHECK(hipGetLastError());
 }
+template void launch_grid_bwd_bwd<_Float16>(hipStream_t, const GridCall&, uint32_t, const float*, uint32_t, const _Float16*, const float*,
+                                            const _Float16*, uint32_t, float*, _Float16*, uint32_t, float*);
+template void launch_grid_bwd_bwd<float>(hipStream_t, const GridCall&, uint32_t, const float*, uint32_t, const float*, const float*,
+                                         const float*, uint32_t, float*, float*, uint32_t, float*);
 
-void launch_grid_bwd_bwd(hipStream_t st, uint32_t D, uint32_t F, HashType h, uint32_t B, uint32_t L, const float* pos,
-                         uint32_t pos_stride, const void* table16, const float* dL_ddLdx, const void* dLdy16, uint32_t dy_stride,
-                         float* grad32, void* dLddLdy16, uint32_t ddy_stride, float* dx, const LevelInfo* levels, bool hash_grid,
-                         Interp interp, const GridOpts& go) {
-	grid_bwd_bwd_t<_Float16>(st, D, F, h, B, L, pos, pos_stride, (const _Float16*)table16, dL_ddLdx, (const _Float16*)dLdy16, dy_stride, grad32,
-	                         (_Float16*)dLddLdy16, ddy_stride, dx, levels, hash_grid, interp, go);
-}
-
-void launch_grid_bwd_bwd_f32(hipStream_t st, uint32_t D, uint32_t F, HashType h, uint32_t B, uint32_t L, const float* pos,
-                             uint32_t pos_stride, const float* table32, const float* dL_ddLdx, const float* dLdy32, uint32_t dy_stride,
-                             float* grad32, float* dLddLdy32, uint32_t ddy_stride, float* dx, const LevelInfo* levels, bool hash_grid,
-                             Interp interp, const GridOpts& go) {
-	grid_bwd_bwd_t<float>(st, D, F, h, B, L, pos, pos_stride, table32, dL_ddLdx, dLdy32, dy_stride, grad32, dLddLdy32, ddy_stride, dx, levels,
-	                      hash_grid, interp, go);
-}
 
 // Diagnostic (TCNN_DEBUG_GRID_TIMES=1): per-workgroup start/end wall clock of the grid backward,
 // printed per work item to stderr after a synchronising copy. Never set in measured runs.
@@ -659,32 +547,38 @@ uint32_t grid_bwd_debug_fallbacks() {
 	return n;
 }
 
-extern template void grid_bwd_f<2>(hipStream_t, uint32_t, HashType, int, uint32_t, dim3, size_t, uint32_t, const float*, uint32_t,
-                                   const _Float16*, const GridSlice*, float*, uint32_t, const LevelInfo*, uint32_t, uint32_t, uint32_t,
-                                   const GridBwdLaunch&);
-extern template void grid_bwd_f<3>(hipStream_t, uint32_t, HashType, int, uint32_t, dim3, size_t, uint32_t, const float*, uint32_t,
-                                   const _Float16*, const GridSlice*, float*, uint32_t, const LevelInfo*, uint32_t, uint32_t, uint32_t,
-                                   const GridBwdLaunch&);
-extern template void grid_bwd_f<4>(hipStream_t, uint32_t, HashType, int, uint32_t, dim3, size_t, uint32_t, const float*, uint32_t,
-                                   const _Float16*, const GridSlice*, float*, uint32_t, const LevelInfo*, uint32_t, uint32_t, uint32_t,
-                                   const GridBwdLaunch&);
+extern template void grid_bwd_d<2>(hipStream_t, uint32_t, HashType, const GridBwdLaunch&);
+extern template void grid_bwd_d<3>(hipStream_t, uint32_t, HashType, const GridBwdLaunch&);
+extern template void grid_bwd_d<4>(hipStream_t, uint32_t, HashType, const GridBwdLaunch&);
 
-void launch_grid_bwd(hipStream_t st, uint32_t D, uint32_t F, HashType h, uint32_t B, const float* pos,
-                     uint32_t pos_stride, const void* dLdy16, int dy_layout, uint32_t dy_stride, const GridSlice* slices,
-                     uint32_t n_slices, uint32_t n_chunks, float* partial, uint32_t partial_stride,
-                     const LevelInfo* levels, bool hash_grid, Interp interp, const GridBwdEpilogue* ep, const GridOpts& go,
-                     const GridSlice* host_slices, const LevelInfo* host_levels, uint32_t n_levels, const float* dy_bound) {
+void launch_grid_bwd(hipStream_t st, const GridCall& gc, uint32_t B, const float* pos, uint32_t pos_stride, const void* dLdy16,
+                     int dy_layout, uint32_t dy_stride, const GridSlice* slices, uint32_t n_slices, uint32_t n_chunks, float* partial,
+                     uint32_t partial_stride, const GridBwdEpilogue* ep, const GridSlice* host_slices, const LevelInfo* host_levels,
+                     const float* dy_bound) {
 	const uint32_t n_tail = (ep && ep->enabled) ? ep->n_mlp_groups : 0u;
 	if (n_tail == 0 && (n_slices == 0 || B == 0)) return;  // callers zero the gradient of empty batches
 	if (B == 0) n_slices = 0;
-	const uint32_t ppc = div_round_up(std::max(B, 1u), n_chunks);
+	const uint32_t n_levels = gc.L;
 	GridBwdLaunch gl{};
+	gl.layout = dy_layout;
+	gl.B = B;
+	gl.pos = pos;
+	gl.pos_stride = pos_stride;
+	gl.dLdy = (const _Float16*)dLdy16;
+	gl.dy_stride = dy_stride;
+	gl.items = slices;
+	gl.partial = partial;
+	gl.partial_stride = partial_stride;
+	gl.levels = gc.levels;
+	gl.hash_grid = gc.hash_grid ? 1u : 0u;
+	gl.interp = (uint32_t)gc.interp;
+	gl.pts_per_chunk = div_round_up(std::max(B, 1u), n_chunks);
 	gl.n_items = n_slices;
 	gl.n_chunks = n_chunks;
 	if (ep) gl.ep = *ep;
 	else gl.ep.enabled = 0;
 	gl.dbg_times = nullptr;
-	gl.opts = go;
+	gl.opts = gc.opts;
 	gl.dy_bound = dy_layout == 0 ? dy_bound : nullptr;
 	gl.fallback_count = nullptr;
 	if (g_count_fallbacks) {
@@ -698,16 +592,10 @@ void launch_grid_bwd(hipStream_t st, uint32_t D, uint32_t F, HashType h, uint32_
 		std::copy(host_slices, host_slices + n_slices, gl.tb.items);
 		std::copy(host_levels, host_levels + n_levels, gl.tb.levels);
 	}
-	dim3 g(n_slices * n_chunks + n_tail);
+	const dim3 g(n_slices * n_chunks + n_tail);
+	gl.n_workgroups = g.x;
 	if (dbg_grid_times()) gl.dbg_times = (unsigned long long*)g_dbg_times.get((size_t)g.x * 64);
-	const size_t lds = GRID_BWD_LDS_BYTES;
-	const _Float16* dy = (const _Float16*)dLdy16;
-	switch (D) {
-		case 2: grid_bwd_f<2>(st, F, h, dy_layout, dy_stride, g, lds, B, pos, pos_stride, dy, slices, partial, partial_stride, levels, hash_grid, (uint32_t)interp, ppc, gl); break;
-		case 3: grid_bwd_f<3>(st, F, h, dy_layout, dy_stride, g, lds, B, pos, pos_stride, dy, slices, partial, partial_stride, levels, hash_grid, (uint32_t)interp, ppc, gl); break;
-		case 4: grid_bwd_f<4>(st, F, h, dy_layout, dy_stride, g, lds, B, pos, pos_stride, dy, slices, partial, partial_stride, levels, hash_grid, (uint32_t)interp, ppc, gl); break;
-		default: throw std::runtime_error("GridEncoding: number of input dims must be 2, 3 or 4");
-	}
+	with_grid_dims(gc.D, [&](auto d) { grid_bwd_d<decltype(d)::value>(st, gc.F, gc.hash, gl); });
 	TCNN_HIP_CHECK(hipGetLastError());
 	if (gl.dbg_times) {
 		std::vector<unsigned long long> t((size_t)g.x * 8);

@@ -26,6 +26,7 @@
 
 #include "adam_device.h"
 #include "grid_device.h"
+#include "grid_dispatch.h"
 
 namespace tcnn_amd {
 
@@ -341,50 +342,21 @@ __global__ __launch_bounds__(ACC_THREADS) void k_grid_acc(int layout, uint32_t B
 }
 
 template <uint32_t D, uint32_t F, HashType H>
-static void grid_bin_t(hipStream_t st, int layout, uint32_t dys, uint32_t B, const float* pos, uint32_t ps, const _Float16* dy,
-                       const LevelInfo* lv, uint32_t hg, uint32_t in, const GridBinArgs& a, const GridOpts& go) {
-	const dim3 g(a.n_slots * a.n_chunks);
-	if (go.active)
-		hipLaunchKernelGGL((k_grid_bin<D, F, H, true>), g, dim3(BIN_THREADS), 0, st, layout, B, pos, ps, dy, dys, lv, hg, in, a, go);
-	else
-		hipLaunchKernelGGL((k_grid_bin<D, F, H, false>), g, dim3(BIN_THREADS), 0, st, layout, B, pos, ps, dy, dys, lv, hg, in, a, go);
+static void grid_bin_t(hipStream_t st, const GridCall& gc, uint32_t B, const float* pos, uint32_t ps, const _Float16* dy, int layout,
+                       uint32_t dys, const GridBinArgs& a) {
+	const auto kernel = gc.opts.active ? k_grid_bin<D, F, H, true> : k_grid_bin<D, F, H, false>;
+	hipLaunchKernelGGL(kernel, dim3(a.n_slots * a.n_chunks), dim3(BIN_THREADS), 0, st, layout, B, pos, ps, dy, dys, gc.levels,
+	                   gc.hash_grid ? 1u : 0u, (uint32_t)gc.interp, a, gc.opts);
 }
 
-template <uint32_t D, uint32_t F>
-static void grid_bin_h(hipStream_t st, HashType h, int layout, uint32_t dys, uint32_t B, const float* pos, uint32_t ps, const _Float16* dy,
-                       const LevelInfo* lv, uint32_t hg, uint32_t in, const GridBinArgs& a, const GridOpts& go) {
-	switch (h) {
-		case HashType::Prime: grid_bin_t<D, F, HashType::Prime>(st, layout, dys, B, pos, ps, dy, lv, hg, in, a, go); break;
-		case HashType::ReversedPrime: grid_bin_t<D, F, HashType::ReversedPrime>(st, layout, dys, B, pos, ps, dy, lv, hg, in, a, go); break;
-		default: grid_bin_t<D, F, HashType::CoherentPrime>(st, layout, dys, B, pos, ps, dy, lv, hg, in, a, go); break;
-	}
-}
-
-template <uint32_t D>
-static void grid_bin_f(hipStream_t st, uint32_t F, HashType h, int layout, uint32_t dys, uint32_t B, const float* pos, uint32_t ps,
-                       const _Float16* dy, const LevelInfo* lv, uint32_t hg, uint32_t in, const GridBinArgs& a, const GridOpts& go) {
-	switch (F) {
-		case 1: grid_bin_h<D, 1>(st, h, layout, dys, B, pos, ps, dy, lv, hg, in, a, go); break;
-		case 2: grid_bin_h<D, 2>(st, h, layout, dys, B, pos, ps, dy, lv, hg, in, a, go); break;
-		case 4: grid_bin_h<D, 4>(st, h, layout, dys, B, pos, ps, dy, lv, hg, in, a, go); break;
-		case 8: grid_bin_h<D, 8>(st, h, layout, dys, B, pos, ps, dy, lv, hg, in, a, go); break;
-		default: throw std::runtime_error("GridEncoding: n_features_per_level must be 1, 2, 4 or 8");
-	}
-}
-
-void launch_grid_bin(hipStream_t st, uint32_t D, uint32_t F, HashType h, uint32_t B, const float* pos, uint32_t pos_stride,
-                     const void* dLdy16, int dy_layout, uint32_t dy_stride, const LevelInfo* levels, bool hash_grid, Interp interp,
-                     const GridBinArgs& a, const GridOpts& go) {
+void launch_grid_bin(hipStream_t st, const GridCall& gc, uint32_t B, const float* pos, uint32_t pos_stride, const void* dLdy16,
+                     int dy_layout, uint32_t dy_stride, const GridBinArgs& a) {
 	if (B == 0 || a.n_slots == 0) return;
-	TCNN_CHECK(a.pts_per_chunk == (GRID_BIN_RECS >> D) && a.n_chunks == div_round_up(B, a.pts_per_chunk), "grid bin: chunk plan mismatch");
-	const _Float16* dy = (const _Float16*)dLdy16;
-	const uint32_t hg = hash_grid ? 1u : 0u, in = (uint32_t)interp;
-	switch (D) {
-		case 2: grid_bin_f<2>(st, F, h, dy_layout, dy_stride, B, pos, pos_stride, dy, levels, hg, in, a, go); break;
-		case 3: grid_bin_f<3>(st, F, h, dy_layout, dy_stride, B, pos, pos_stride, dy, levels, hg, in, a, go); break;
-		case 4: grid_bin_f<4>(st, F, h, dy_layout, dy_stride, B, pos, pos_stride, dy, levels, hg, in, a, go); break;
-		default: throw std::runtime_error("GridEncoding: number of input dims must be 2, 3 or 4");
-	}
+	TCNN_CHECK(a.pts_per_chunk == (GRID_BIN_RECS >> gc.D) && a.n_chunks == div_round_up(B, a.pts_per_chunk), "grid bin: chunk plan mismatch");
+	with_grid_shape(gc.D, gc.F, gc.hash, [&](auto d, auto f, auto h) {
+		grid_bin_t<decltype(d)::value, decltype(f)::value, decltype(h)::value>(st, gc, B, pos, pos_stride, (const _Float16*)dLdy16, dy_layout,
+		                                                                       dy_stride, a);
+	});
 	TCNN_HIP_CHECK(hipGetLastError());
 }
 
@@ -402,28 +374,16 @@ static void grid_acc_t(hipStream_t st, int layout, uint32_t dys, uint32_t B, con
 	                   ad ? 1 : 0);
 }
 
-template <uint32_t NC>
-static void grid_acc_f(hipStream_t st, uint32_t F, int layout, uint32_t dys, uint32_t B, const _Float16* dy, const LevelInfo* lv,
-                       const GridBinArgs& a, float* grad32, const GridAccAdam* ad) {
-	switch (F) {
-		case 1: grid_acc_t<NC, 1>(st, layout, dys, B, dy, lv, a, grad32, ad); break;
-		case 2: grid_acc_t<NC, 2>(st, layout, dys, B, dy, lv, a, grad32, ad); break;
-		case 4: grid_acc_t<NC, 4>(st, layout, dys, B, dy, lv, a, grad32, ad); break;
-		case 8: grid_acc_t<NC, 8>(st, layout, dys, B, dy, lv, a, grad32, ad); break;
-		default: throw std::runtime_error("GridEncoding: n_features_per_level must be 1, 2, 4 or 8");
-	}
-}
-
-void launch_grid_acc(hipStream_t st, uint32_t D, uint32_t F, uint32_t B, const void* dLdy16, int dy_layout, uint32_t dy_stride,
-                     const LevelInfo* levels, const GridBinArgs& a, float* grad32, const GridAccAdam* adam) {
+// the accumulate pass does not index the grid (the records carry the entries): corners per point x features
+void launch_grid_acc(hipStream_t st, const GridCall& gc, uint32_t B, const void* dLdy16, int dy_layout, uint32_t dy_stride,
+                     const GridBinArgs& a, float* grad32, const GridAccAdam* adam) {
 	if (a.n_slots == 0 || a.n_buckets == 0) return;
-	const _Float16* dy = (const _Float16*)dLdy16;
-	switch (D) {
-		case 2: grid_acc_f<4>(st, F, dy_layout, dy_stride, B, dy, levels, a, grad32, adam); break;
-		case 3: grid_acc_f<8>(st, F, dy_layout, dy_stride, B, dy, levels, a, grad32, adam); break;
-		case 4: grid_acc_f<16>(st, F, dy_layout, dy_stride, B, dy, levels, a, grad32, adam); break;
-		default: throw std::runtime_error("GridEncoding: number of input dims must be 2, 3 or 4");
-	}
+	with_grid_dims(gc.D, [&](auto d) {
+		with_grid_features(gc.F, [&](auto f) {
+			grid_acc_t<(1u << decltype(d)::value), decltype(f)::value>(st, dy_layout, dy_stride, B, (const _Float16*)dLdy16, gc.levels, a, grad32,
+			                                                          adam);
+		});
+	});
 	TCNN_HIP_CHECK(hipGetLastError());
 }
 

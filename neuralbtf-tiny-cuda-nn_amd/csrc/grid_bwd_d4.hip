@@ -2,7 +2,5 @@
 #include "grid_bwd_lds.h"
 
 namespace tcnn_amd {
-template void grid_bwd_f<4>(hipStream_t, uint32_t, HashType, int, uint32_t, dim3, size_t, uint32_t, const float*, uint32_t,
-                             const _Float16*, const GridSlice*, float*, uint32_t, const LevelInfo*, uint32_t, uint32_t, uint32_t,
-                             const GridBwdLaunch&);
+template void grid_bwd_d<4>(hipStream_t, uint32_t, HashType, const GridBwdLaunch&);
 }  // namespace tcnn_amd

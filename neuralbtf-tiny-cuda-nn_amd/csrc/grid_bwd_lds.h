@@ -13,6 +13,7 @@
 #include "adam_device.h"
 #include "grid_bwd_scale.h"
 #include "grid_device.h"
+#include "grid_dispatch.h"
 
 namespace tcnn_amd {
 
@@ -719,7 +720,21 @@ __global__ __launch_bounds__(GRID_BWD_THREADS) void k_grid_bwd_lds(
 	}
 }
 
+// One launch of k_grid_bwd_lds: its grid and its arguments, in the kernel's parameter order
+// (launch_grid_bwd in grid.hip fills it; grid_bwd_d<D> picks the instantiation).
 struct GridBwdLaunch {
+	uint32_t n_workgroups;  // n_items * n_chunks + the epilogue's tail workgroups
+	int layout;
+	uint32_t B;
+	const float* pos;
+	uint32_t pos_stride;
+	const _Float16* dLdy;
+	uint32_t dy_stride;
+	const GridSlice* items;
+	float* partial;
+	uint32_t partial_stride;
+	const LevelInfo* levels;
+	uint32_t hash_grid, interp, pts_per_chunk;
 	uint32_t n_items, n_chunks;
 	GridBwdEpilogue ep;
 	unsigned long long* dbg_times;
@@ -730,43 +745,23 @@ struct GridBwdLaunch {
 };
 
 template <uint32_t D, uint32_t F, HashType H>
-static void grid_bwd_t(hipStream_t st, int layout, uint32_t dys, dim3 g, size_t lds, uint32_t B, const float* pos, uint32_t ps,
-                       const _Float16* dy, const GridSlice* sl, float* part, uint32_t pstr, const LevelInfo* lv,
-                       uint32_t hg, uint32_t in, uint32_t ppc, const GridBwdLaunch& gl) {
+static void grid_bwd_t(hipStream_t st, const GridBwdLaunch& gl) {
 	// the options (max_level, stochastic) are a separate instantiation: the default kernel stays lean
 	static uint64_t done0 = 0, done1 = 0;
 	set_dyn_lds((const void*)k_grid_bwd_lds<D, F, H, false>, (int)GRID_BWD_LDS_BYTES, done0);
 	set_dyn_lds((const void*)k_grid_bwd_lds<D, F, H, true>, (int)GRID_BWD_LDS_BYTES, done1);
-	if (gl.opts.active)
-		hipLaunchKernelGGL((k_grid_bwd_lds<D, F, H, true>), g, dim3(GRID_BWD_THREADS), lds, st, layout, B, pos, ps, dy, dys, sl, part, pstr, lv, hg, in,
-		                   ppc, gl.n_items, gl.n_chunks, gl.ep, gl.dbg_times, gl.opts, gl.tb, gl.dy_bound, gl.fallback_count);
-	else
-		hipLaunchKernelGGL((k_grid_bwd_lds<D, F, H, false>), g, dim3(GRID_BWD_THREADS), lds, st, layout, B, pos, ps, dy, dys, sl, part, pstr, lv, hg, in,
-		                   ppc, gl.n_items, gl.n_chunks, gl.ep, gl.dbg_times, gl.opts, gl.tb, gl.dy_bound, gl.fallback_count);
+	const auto kernel = gl.opts.active ? k_grid_bwd_lds<D, F, H, true> : k_grid_bwd_lds<D, F, H, false>;
+	hipLaunchKernelGGL(kernel, dim3(gl.n_workgroups), dim3(GRID_BWD_THREADS), GRID_BWD_LDS_BYTES, st, gl.layout, gl.B, gl.pos, gl.pos_stride,
+	                   gl.dLdy, gl.dy_stride, gl.items, gl.partial, gl.partial_stride, gl.levels, gl.hash_grid, gl.interp, gl.pts_per_chunk,
+	                   gl.n_items, gl.n_chunks, gl.ep, gl.dbg_times, gl.opts, gl.tb, gl.dy_bound, gl.fallback_count);
 }
 
-template <uint32_t D, uint32_t F>
-static void grid_bwd_h(hipStream_t st, HashType h, int pairs, uint32_t dys, dim3 g, size_t lds, uint32_t B, const float* pos, uint32_t ps,
-                       const _Float16* dy, const GridSlice* sl, float* part, uint32_t pstr, const LevelInfo* lv,
-                       uint32_t hg, uint32_t in, uint32_t ppc, const GridBwdLaunch& gl) {
-	switch (h) {
-		case HashType::Prime: grid_bwd_t<D, F, HashType::Prime>(st, pairs, dys, g, lds, B, pos, ps, dy, sl, part, pstr, lv, hg, in, ppc, gl); break;
-		case HashType::ReversedPrime: grid_bwd_t<D, F, HashType::ReversedPrime>(st, pairs, dys, g, lds, B, pos, ps, dy, sl, part, pstr, lv, hg, in, ppc, gl); break;
-		default: grid_bwd_t<D, F, HashType::CoherentPrime>(st, pairs, dys, g, lds, B, pos, ps, dy, sl, part, pstr, lv, hg, in, ppc, gl); break;
-	}
-}
-
+// every (F, hash) instantiation of one D: instantiated in grid_bwd_d{2,3,4}.hip only
 template <uint32_t D>
-void grid_bwd_f(hipStream_t st, uint32_t F, HashType h, int pairs, uint32_t dys, dim3 g, size_t lds, uint32_t B, const float* pos,
-                       uint32_t ps, const _Float16* dy, const GridSlice* sl, float* part, uint32_t pstr, const LevelInfo* lv,
-                       uint32_t hg, uint32_t in, uint32_t ppc, const GridBwdLaunch& gl) {
-	switch (F) {
-		case 1: grid_bwd_h<D, 1>(st, h, pairs, dys, g, lds, B, pos, ps, dy, sl, part, pstr, lv, hg, in, ppc, gl); break;
-		case 2: grid_bwd_h<D, 2>(st, h, pairs, dys, g, lds, B, pos, ps, dy, sl, part, pstr, lv, hg, in, ppc, gl); break;
-		case 4: grid_bwd_h<D, 4>(st, h, pairs, dys, g, lds, B, pos, ps, dy, sl, part, pstr, lv, hg, in, ppc, gl); break;
-		case 8: grid_bwd_h<D, 8>(st, h, pairs, dys, g, lds, B, pos, ps, dy, sl, part, pstr, lv, hg, in, ppc, gl); break;
-		default: throw std::runtime_error("GridEncoding: n_features_per_level must be 1, 2, 4 or 8");
-	}
+void grid_bwd_d(hipStream_t st, uint32_t F, HashType h, const GridBwdLaunch& gl) {
+	with_grid_features(F, [&](auto f) {
+		with_grid_hash(h, [&](auto hh) { grid_bwd_t<D, decltype(f)::value, decltype(hh)::value>(st, gl); });
+	});
 }
 
 }  // namespace tcnn_amd

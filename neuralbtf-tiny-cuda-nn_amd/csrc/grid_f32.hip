@@ -12,6 +12,7 @@
 
 #include "grid_bwd_lds.h"
 #include "grid_device.h"
+#include "grid_dispatch.h"
 
 namespace tcnn_amd {
 
@@ -108,49 +109,22 @@ __global__ __launch_bounds__(256) void k_grid_fwd_f32(uint32_t B, const float* _
 	}
 }
 
-template <uint32_t D, uint32_t F>
-static void grid_fwd_f32_h(hipStream_t st, HashType h, uint32_t B, const float* pos, uint32_t ps, const float* t, float* o, uint32_t os,
-                           const LevelInfo* lv, uint32_t hg, uint32_t in, const GridOpts& go, uint32_t L, uint32_t vec) {
-	constexpr uint32_t G = F >= 4 ? 1 : 4 / F;
-	const uint64_t n = (uint64_t)B * ((L + G - 1) / G);
-	TCNN_CHECK(n < (1ull << 32), "GridEncoding: batch too large for one fp32 forward launch");
-	const dim3 g(div_round_up(n, 256));
-#define GF32_LAUNCH(HH) hipLaunchKernelGGL((k_grid_fwd_f32<D, F, HH>), g, dim3(256), 0, st, B, pos, ps, t, o, os, lv, hg, in, go, L, vec)
-	switch (h) {
-		case HashType::Prime: GF32_LAUNCH(HashType::Prime); break;
-		case HashType::ReversedPrime: GF32_LAUNCH(HashType::ReversedPrime); break;
-		default: GF32_LAUNCH(HashType::CoherentPrime); break;
-	}
-#undef GF32_LAUNCH
-}
-
-template <uint32_t D>
-static void grid_fwd_f32_f(hipStream_t st, uint32_t F, HashType h, uint32_t B, const float* pos, uint32_t ps, const float* t, float* o,
-                           uint32_t os, const LevelInfo* lv, uint32_t hg, uint32_t in, const GridOpts& go, uint32_t L) {
-	// FVec loads: entry e sits at table + e F, so the base decides; 16-byte row stores: base and stride
-	const uint32_t tb = std::min(F * 4u, 16u);
-	const uint32_t vec = (((uintptr_t)t % tb) == 0 ? 1u : 0u) | ((((uintptr_t)o % 16) == 0 && os % 4 == 0) ? 2u : 0u);
-	switch (F) {
-		case 1: grid_fwd_f32_h<D, 1>(st, h, B, pos, ps, t, o, os, lv, hg, in, go, L, vec); break;
-		case 2: grid_fwd_f32_h<D, 2>(st, h, B, pos, ps, t, o, os, lv, hg, in, go, L, vec); break;
-		case 4: grid_fwd_f32_h<D, 4>(st, h, B, pos, ps, t, o, os, lv, hg, in, go, L, vec); break;
-		case 8: grid_fwd_f32_h<D, 8>(st, h, B, pos, ps, t, o, os, lv, hg, in, go, L, vec); break;
-		default: throw std::runtime_error("GridEncoding: n_features_per_level must be 1, 2, 4 or 8");
-	}
-}
-
-void launch_grid_fwd_f32(hipStream_t st, uint32_t D, uint32_t F, HashType h, uint32_t B, uint32_t L, const float* pos,
-                         uint32_t pos_stride, const float* table32, float* out32, uint32_t out_stride, const LevelInfo* levels,
-                         bool hash_grid, Interp interp, const GridOpts& go) {
+void launch_grid_fwd_f32(hipStream_t st, const GridCall& gc, uint32_t B, const float* pos, uint32_t pos_stride, const float* table32,
+                         float* out32, uint32_t out_stride) {
 	if (B == 0) return;
-	TCNN_CHECK(L * F <= out_stride, "GridEncoding: fp32 rows narrower than the grid's features");
-	const uint32_t hg = hash_grid ? 1u : 0u, in = (uint32_t)interp;
-	switch (D) {
-		case 2: grid_fwd_f32_f<2>(st, F, h, B, pos, pos_stride, table32, out32, out_stride, levels, hg, in, go, L); break;
-		case 3: grid_fwd_f32_f<3>(st, F, h, B, pos, pos_stride, table32, out32, out_stride, levels, hg, in, go, L); break;
-		case 4: grid_fwd_f32_f<4>(st, F, h, B, pos, pos_stride, table32, out32, out_stride, levels, hg, in, go, L); break;
-		default: throw std::runtime_error("GridEncoding: number of input dims must be 2, 3 or 4");
-	}
+	TCNN_CHECK(gc.L * gc.F <= out_stride, "GridEncoding: fp32 rows narrower than the grid's features");
+	with_grid_shape(gc.D, gc.F, gc.hash, [&](auto d, auto f, auto h) {
+		constexpr uint32_t D = decltype(d)::value, F = decltype(f)::value;
+		constexpr HashType H = decltype(h)::value;
+		// FVec loads: entry e sits at table + e F, so the base decides; 16-byte row stores: base and stride
+		constexpr uint32_t tb = F * 4u < 16u ? F * 4u : 16u;
+		const uint32_t vec = (((uintptr_t)table32 % tb) == 0 ? 1u : 0u) | ((((uintptr_t)out32 % 16) == 0 && out_stride % 4 == 0) ? 2u : 0u);
+		constexpr uint32_t G = F >= 4 ? 1 : 4 / F;  // levels per thread (k_grid_fwd_f32)
+		const uint64_t n = (uint64_t)B * ((gc.L + G - 1) / G);
+		TCNN_CHECK(n < (1ull << 32), "GridEncoding: batch too large for one fp32 forward launch");
+		hipLaunchKernelGGL((k_grid_fwd_f32<D, F, H>), dim3(div_round_up(n, 256)), dim3(256), 0, st, B, pos, pos_stride, table32, out32,
+		                   out_stride, gc.levels, gc.hash_grid ? 1u : 0u, (uint32_t)gc.interp, gc.opts, gc.L, vec);
+	});
 	TCNN_HIP_CHECK(hipGetLastError());
 }
 
@@ -389,60 +363,26 @@ __global__ __launch_bounds__(GRID_BWD_THREADS) void k_grid_bwd_lds_f32(
 }
 
 template <uint32_t D, uint32_t F, HashType H>
-static void grid_bwd_f32_t(hipStream_t st, dim3 g, uint32_t B, const float* pos, uint32_t ps, const float* dy, uint32_t dys, uint32_t vec,
-                           const GridSlice* sl, float* part, uint32_t pstr, const LevelInfo* lv, uint32_t hg, uint32_t in, uint32_t ppc,
-                           uint32_t n_chunks, const GridOpts& go) {
+static void grid_bwd_f32_t(hipStream_t st, const GridCall& gc, uint32_t B, const float* pos, uint32_t ps, const float* dy, uint32_t dys,
+                           const GridSlice* sl, uint32_t n_slices, uint32_t n_chunks, float* part, uint32_t pstr) {
 	static uint64_t done0 = 0, done1 = 0;
 	set_dyn_lds((const void*)k_grid_bwd_lds_f32<D, F, H, false>, (int)GRID_BWD_LDS_BYTES, done0);
 	set_dyn_lds((const void*)k_grid_bwd_lds_f32<D, F, H, true>, (int)GRID_BWD_LDS_BYTES, done1);
-	if (go.active)
-		hipLaunchKernelGGL((k_grid_bwd_lds_f32<D, F, H, true>), g, dim3(GRID_BWD_THREADS), GRID_BWD_LDS_BYTES, st, B, pos, ps, dy, dys, vec, sl,
-		                   part, pstr, lv, hg, in, ppc, n_chunks, go);
-	else
-		hipLaunchKernelGGL((k_grid_bwd_lds_f32<D, F, H, false>), g, dim3(GRID_BWD_THREADS), GRID_BWD_LDS_BYTES, st, B, pos, ps, dy, dys, vec, sl,
-		                   part, pstr, lv, hg, in, ppc, n_chunks, go);
-}
-
-template <uint32_t D, uint32_t F>
-static void grid_bwd_f32_h(hipStream_t st, HashType h, dim3 g, uint32_t B, const float* pos, uint32_t ps, const float* dy, uint32_t dys,
-                           const GridSlice* sl, float* part, uint32_t pstr, const LevelInfo* lv, uint32_t hg, uint32_t in, uint32_t ppc,
-                           uint32_t n_chunks, const GridOpts& go) {
-	const uint32_t tb = std::min(F * 4u, 16u);
+	constexpr uint32_t tb = F * 4u < 16u ? F * 4u : 16u;
 	const uint32_t vec = ((uintptr_t)dy % tb == 0 && (dys * 4u) % tb == 0) ? 1u : 0u;  // every row's level slice is FVec-aligned
-	switch (h) {
-		case HashType::Prime: grid_bwd_f32_t<D, F, HashType::Prime>(st, g, B, pos, ps, dy, dys, vec, sl, part, pstr, lv, hg, in, ppc, n_chunks, go); break;
-		case HashType::ReversedPrime: grid_bwd_f32_t<D, F, HashType::ReversedPrime>(st, g, B, pos, ps, dy, dys, vec, sl, part, pstr, lv, hg, in, ppc, n_chunks, go); break;
-		default: grid_bwd_f32_t<D, F, HashType::CoherentPrime>(st, g, B, pos, ps, dy, dys, vec, sl, part, pstr, lv, hg, in, ppc, n_chunks, go); break;
-	}
+	const auto kernel = gc.opts.active ? k_grid_bwd_lds_f32<D, F, H, true> : k_grid_bwd_lds_f32<D, F, H, false>;
+	hipLaunchKernelGGL(kernel, dim3(n_slices * n_chunks), dim3(GRID_BWD_THREADS), GRID_BWD_LDS_BYTES, st, B, pos, ps, dy, dys, vec, sl, part,
+	                   pstr, gc.levels, gc.hash_grid ? 1u : 0u, (uint32_t)gc.interp, div_round_up(B, n_chunks), n_chunks, gc.opts);
 }
 
-template <uint32_t D>
-static void grid_bwd_f32_f(hipStream_t st, uint32_t F, HashType h, dim3 g, uint32_t B, const float* pos, uint32_t ps, const float* dy,
-                           uint32_t dys, const GridSlice* sl, float* part, uint32_t pstr, const LevelInfo* lv, uint32_t hg, uint32_t in,
-                           uint32_t ppc, uint32_t n_chunks, const GridOpts& go) {
-	switch (F) {
-		case 1: grid_bwd_f32_h<D, 1>(st, h, g, B, pos, ps, dy, dys, sl, part, pstr, lv, hg, in, ppc, n_chunks, go); break;
-		case 2: grid_bwd_f32_h<D, 2>(st, h, g, B, pos, ps, dy, dys, sl, part, pstr, lv, hg, in, ppc, n_chunks, go); break;
-		case 4: grid_bwd_f32_h<D, 4>(st, h, g, B, pos, ps, dy, dys, sl, part, pstr, lv, hg, in, ppc, n_chunks, go); break;
-		case 8: grid_bwd_f32_h<D, 8>(st, h, g, B, pos, ps, dy, dys, sl, part, pstr, lv, hg, in, ppc, n_chunks, go); break;
-		default: throw std::runtime_error("GridEncoding: n_features_per_level must be 1, 2, 4 or 8");
-	}
-}
-
-void launch_grid_bwd_f32(hipStream_t st, uint32_t D, uint32_t F, HashType h, uint32_t B, const float* pos, uint32_t pos_stride,
-                         const float* dLdy32, uint32_t dy_stride, const GridSlice* slices, uint32_t n_slices, uint32_t n_chunks,
-                         float* partial, uint32_t partial_stride, const LevelInfo* levels, bool hash_grid, Interp interp,
-                         const GridOpts& go) {
+void launch_grid_bwd_f32(hipStream_t st, const GridCall& gc, uint32_t B, const float* pos, uint32_t pos_stride, const float* dLdy32,
+                         uint32_t dy_stride, const GridSlice* slices, uint32_t n_slices, uint32_t n_chunks, float* partial,
+                         uint32_t partial_stride) {
 	if (n_slices == 0 || B == 0) return;  // callers zero the gradient of empty batches
-	const uint32_t ppc = div_round_up(B, n_chunks);
-	const dim3 g(n_slices * n_chunks);
-	const uint32_t hg = hash_grid ? 1u : 0u, in = (uint32_t)interp;
-	switch (D) {
-		case 2: grid_bwd_f32_f<2>(st, F, h, g, B, pos, pos_stride, dLdy32, dy_stride, slices, partial, partial_stride, levels, hg, in, ppc, n_chunks, go); break;
-		case 3: grid_bwd_f32_f<3>(st, F, h, g, B, pos, pos_stride, dLdy32, dy_stride, slices, partial, partial_stride, levels, hg, in, ppc, n_chunks, go); break;
-		case 4: grid_bwd_f32_f<4>(st, F, h, g, B, pos, pos_stride, dLdy32, dy_stride, slices, partial, partial_stride, levels, hg, in, ppc, n_chunks, go); break;
-		default: throw std::runtime_error("GridEncoding: number of input dims must be 2, 3 or 4");
-	}
+	with_grid_shape(gc.D, gc.F, gc.hash, [&](auto d, auto f, auto h) {
+		grid_bwd_f32_t<decltype(d)::value, decltype(f)::value, decltype(h)::value>(st, gc, B, pos, pos_stride, dLdy32, dy_stride, slices,
+		                                                                           n_slices, n_chunks, partial, partial_stride);
+	});
 	TCNN_HIP_CHECK(hipGetLastError());
 }
 

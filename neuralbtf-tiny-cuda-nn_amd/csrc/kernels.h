@@ -7,6 +7,17 @@ namespace tcnn_amd {
 
 struct LevelInfo;
 
+// What every grid launcher needs to know about the grid it runs on (GridEncodingHost::call()): the
+// shape that selects the kernel (grid_dispatch.h), the device level table and the options.
+struct GridCall {
+	uint32_t D, F, L;  // input dims, features per level, levels
+	HashType hash;
+	bool hash_grid;    // GridType::Hash (dense and tiled grids index without hashing)
+	Interp interp;
+	const LevelInfo* levels;  // device [L]
+	GridOpts opts;
+};
+
 // Work plan of the LDS-privatised grid backward: one item per (level, entry range, feature range);
 // the item's int32 accumulators (end-begin) x nf fit in grid_bwd_slot_budget() LDS slots.
 struct GridSlice {
@@ -145,11 +156,12 @@ bool fused_train_supported(uint32_t W, uint32_t IN, uint32_t NH, uint32_t D, uin
 // Workgroups the fused launch uses (= partial slabs it writes) for this shape and batch.
 uint32_t fused_train_waves();  // waves per workgroup of k_fused_train_grid
 uint32_t fused_train_n_blocks(uint32_t W, uint32_t IN, uint32_t NH, uint32_t D, uint32_t dims, bool ext_dout, uint32_t B);
-void launch_fused_train(hipStream_t st, uint32_t W, uint32_t IN, uint32_t NH, uint32_t D, HashType h, int act,
+// g: the grid (D, hash, levels, hash_grid, interp and opts.inrange_index are read).
+void launch_fused_train(hipStream_t st, const GridCall& g, uint32_t W, uint32_t IN, uint32_t NH, int act,
                         uint32_t B, uint32_t dims, float loss_scale, const void* params16, const void* table16,
                         const float* pos, const float* target, void* out16, void* dLdenc_pairs,
-                        float* wgrad_partial, float* loss_partial, const LevelInfo* levels, bool hash_grid,
-                        Interp interp, uint32_t n_blocks, const void* dout16, const void* wimage, uint32_t loss_type = 0, bool inrange_index = false,
+                        float* wgrad_partial, float* loss_partial, uint32_t n_blocks, const void* dout16, const void* wimage,
+                        uint32_t loss_type = 0,
                         const void* enc16 = nullptr,  // enc16: the encoding read from memory, SoA [IN][B] (no gathers)
                         float dout_scale = 1.0f,      // dout16 is used as fp16(dout16 * dout_scale)
                         float* dy_bound = nullptr);   // [L][B/32] slice sums of max_f |dL/denc| (grid_bwd_lds.h); null: none
@@ -161,9 +173,8 @@ void launch_pack_weights(hipStream_t st, uint32_t W, uint32_t IN, uint32_t NH, c
 bool mlp_infer_supported(uint32_t W, uint32_t IN, uint32_t NH, uint32_t OUTP, int act);
 // grid encoding + MLP forward in one kernel (k_fused_fwd_grid); wimage null: the LDS image is built from
 // params16 (16-byte aligned); enc16 (nullable) receives the SoA encoding
-void launch_fused_fwd(hipStream_t st, uint32_t W, uint32_t IN, uint32_t NH, uint32_t D, HashType h, int act, uint32_t B,
-                      const void* wimage, const void* params16, const void* table16, const float* pos, const LevelInfo* levels, bool hash_grid,
-                      Interp interp, bool inrange_index, void* enc16, void* out16);
+void launch_fused_fwd(hipStream_t st, const GridCall& g, uint32_t W, uint32_t IN, uint32_t NH, int act, uint32_t B,
+                      const void* wimage, const void* params16, const void* table16, const float* pos, void* enc16, void* out16);
 void launch_mlp_infer(hipStream_t st, uint32_t W, uint32_t IN, uint32_t NH, int act, bool soa, uint32_t B,
                       const void* wimage, const void* in16, void* out16);
 // out[b*n_out + o] = (float)in[b*in_stride + o]  (reference trim_and_cast_from, object.cu:60-67)
@@ -171,22 +182,18 @@ void launch_trim_cast(hipStream_t st, uint32_t B, uint32_t in_stride, uint32_t n
 
 // Grid forward (standalone; reference kernel_grid layout): out SoA [(l*F+f)*B + i] when soa, else
 // AoS [i*out_stride + l*F + f].
-void launch_grid_fwd(hipStream_t st, uint32_t D, uint32_t F, HashType h, uint32_t B, uint32_t L,
-                     const float* pos, uint32_t pos_stride, const void* table16, void* out16, bool soa,
-                     uint32_t out_stride, const LevelInfo* levels, bool hash_grid, Interp interp, const GridOpts& opts = GridOpts{},
-                     uint32_t aos_row_cols = 0);
+void launch_grid_fwd(hipStream_t st, const GridCall& g, uint32_t B, const float* pos, uint32_t pos_stride, const void* table16,
+                     void* out16, bool soa, uint32_t out_stride, uint32_t aos_row_cols = 0);
 
 // Grid backward: dLdy layout 0 = level-major pairs ([l][i][F] halves), 1 = SoA ([(l*F+f)*B + i]),
 // 2 = AoS ([i*dy_stride + l*F + f]).
 uint32_t grid_bwd_slot_budget();
-// host_slices / host_levels: the work plan's host copies, passed by value as kernel arguments when
-// they fit (grid_bwd_lds.h GridBwdTables)
-void launch_grid_bwd(hipStream_t st, uint32_t D, uint32_t F, HashType h, uint32_t B, const float* pos,
-                     uint32_t pos_stride, const void* dLdy16, int dy_layout, uint32_t dy_stride, const GridSlice* slices,
-                     uint32_t n_slices, uint32_t n_chunks, float* partial, uint32_t partial_stride,
-                     const LevelInfo* levels, bool hash_grid, Interp interp, const GridBwdEpilogue* ep = nullptr,
-                     const GridOpts& opts = GridOpts{}, const GridSlice* host_slices = nullptr, const LevelInfo* host_levels = nullptr,
-                     uint32_t n_levels = 0,
+// host_slices / host_levels: the host copies of the work plan and of the g.L levels, passed by value as
+// kernel arguments when they fit (grid_bwd_lds.h GridBwdTables)
+void launch_grid_bwd(hipStream_t st, const GridCall& g, uint32_t B, const float* pos, uint32_t pos_stride, const void* dLdy16,
+                     int dy_layout, uint32_t dy_stride, const GridSlice* slices, uint32_t n_slices, uint32_t n_chunks, float* partial,
+                     uint32_t partial_stride, const GridBwdEpilogue* ep = nullptr, const GridSlice* host_slices = nullptr,
+                     const LevelInfo* host_levels = nullptr,
                      // dy_bound (layout 0 only): [L][B/32] slice sums of max_f |dL/dy| written by the fused kernel that
                      // wrote dLdy16 (launch_fused_train) -- the streaming pre-pass of grid_bwd_lds.h; null: the exact one
                      const float* dy_bound = nullptr);
@@ -195,9 +202,8 @@ void launch_grid_bwd(hipStream_t st, uint32_t D, uint32_t F, HashType h, uint32_
 void grid_bwd_debug_count_fallbacks(bool on);
 uint32_t grid_bwd_debug_fallbacks();
 // Binned backward, pass 1: counting-sort the updates of the binned levels by slice (GridBinArgs).
-void launch_grid_bin(hipStream_t st, uint32_t D, uint32_t F, HashType h, uint32_t B, const float* pos, uint32_t pos_stride,
-                     const void* dLdy16, int dy_layout, uint32_t dy_stride, const LevelInfo* levels, bool hash_grid, Interp interp,
-                     const GridBinArgs& a, const GridOpts& opts = GridOpts{});
+void launch_grid_bin(hipStream_t st, const GridCall& g, uint32_t B, const float* pos, uint32_t pos_stride, const void* dLdy16,
+                     int dy_layout, uint32_t dy_stride, const GridBinArgs& a);
 // Binned backward, pass 2: one workgroup per slice sums its records in LDS (int32 fixed point scaled
 // by the level's sum of |dL/dy|) and writes the fp32 gradient of grid parameter p to grad32[p] (grid
 // parameter order) or, with adam != nullptr, applies Adam to parameter param_base + p.
@@ -207,21 +213,25 @@ struct GridAccAdam {
 	uint32_t param_base;
 	int write_grad32;  // also store the fp32 sum into buf.g32
 };
-void launch_grid_acc(hipStream_t st, uint32_t D, uint32_t F, uint32_t B, const void* dLdy16, int dy_layout, uint32_t dy_stride,
-                     const LevelInfo* levels, const GridBinArgs& a, float* grad32, const GridAccAdam* adam);
+void launch_grid_acc(hipStream_t st, const GridCall& g, uint32_t B, const void* dLdy16, int dy_layout, uint32_t dy_stride,
+                     const GridBinArgs& a, float* grad32, const GridAccAdam* adam);
+
+// The launchers below are typed on the module's precision T (_Float16, or float for an fp32 encoding
+// module: Encoding dtype = float32): the type of the table / the encoded rows / dL/dy. Both forms are
+// instantiated where the kernels are; the arithmetic in between is fp32 in both.
 
 // dL/dx fp32 [B][dx_stride] through the grid (reference grid.h:171-211 + 322-349), dy_dx recomputed
-// from the table; dLdy in the launch_grid_bwd layouts.
-void launch_grid_bwd_input(hipStream_t st, uint32_t D, uint32_t F, HashType h, uint32_t B, uint32_t L, const float* pos,
-                           uint32_t pos_stride, const void* table16, const void* dLdy16, int dy_layout, uint32_t dy_stride, float* dx,
-                           uint32_t dx_stride, const LevelInfo* levels, bool hash_grid, Interp interp, const GridOpts& opts = GridOpts{});
+// from the table; dLdy in the launch_grid_bwd layouts (fp32: AoS rows only, dy_layout 2).
+template <typename T>
+void launch_grid_bwd_input(hipStream_t st, const GridCall& g, uint32_t B, const float* pos, uint32_t pos_stride, const T* table,
+                           const T* dLdy, int dy_layout, uint32_t dy_stride, float* dx, uint32_t dx_stride);
 // Second-order grid gradients (reference grid.h:351-627, 902-1026): from dL/d(dL/dx) fp32 [B][D]
-// and dL/dy (AoS fp16 [B][dy_stride], nullable) -> grad32 += dL/dgrid (fp32 atomics, nullable),
-// dL/d(dL/dy) AoS fp16 [B][ddy_stride] (nullable), dL/dx fp32 [B][D] (nullable).
-void launch_grid_bwd_bwd(hipStream_t st, uint32_t D, uint32_t F, HashType h, uint32_t B, uint32_t L, const float* pos,
-                         uint32_t pos_stride, const void* table16, const float* dL_ddLdx, const void* dLdy16, uint32_t dy_stride,
-                         float* grad32, void* dLddLdy16, uint32_t ddy_stride, float* dx, const LevelInfo* levels, bool hash_grid,
-                         Interp interp, const GridOpts& opts = GridOpts{});
+// and dL/dy (AoS [B][dy_stride], nullable) -> grad32 += dL/dgrid (fp32 atomics, nullable),
+// dL/d(dL/dy) AoS [B][ddy_stride] (nullable), dL/dx fp32 [B][D] (nullable).
+template <typename T>
+void launch_grid_bwd_bwd(hipStream_t st, const GridCall& g, uint32_t B, const float* pos, uint32_t pos_stride, const T* table,
+                         const float* dL_ddLdx, const T* dLdy, uint32_t dy_stride, float* grad32, T* dLddLdy, uint32_t ddy_stride,
+                         float* dx);
 // fused weight-image geometry (FusedLayout) for the epilogue
 void fused_image_layout(uint32_t W, uint32_t IN, uint32_t NH, uint32_t* RSI, uint32_t* RSW, uint32_t* oWh, uint32_t* oWo);
 
@@ -321,15 +331,19 @@ void launch_relative_l2_partial(hipStream_t st, uint32_t B, uint32_t stride, uin
 // out[i] += in[i] (Accumulate-mode gradients)
 void launch_add_f32(hipStream_t st, const float* in, float* out, size_t n);
 
-// ---- OneBlob / Identity encodings (encodings.hip); output AoS fp16 [B][out_stride], padding = 1 ----
-void launch_oneblob_fwd(hipStream_t st, uint32_t B, uint32_t D, uint32_t n_bins, const float* x, uint32_t x_stride, void* out16,
+// ---- OneBlob / Identity encodings (encodings.hip); output AoS [B][out_stride] of T (_Float16 / float), padding = 1 ----
+template <typename T>
+void launch_oneblob_fwd(hipStream_t st, uint32_t B, uint32_t D, uint32_t n_bins, const float* x, uint32_t x_stride, T* out,
                         uint32_t out_stride, uint32_t n_pad);
-// dL/dx fp32 [B][x_stride] from dL/dy fp16 AoS (kernel_one_blob_backward, oneblob.h:116-147)
-void launch_oneblob_bwd(hipStream_t st, uint32_t B, uint32_t D, uint32_t n_bins, const float* x, uint32_t x_stride,
-                        const void* dy16, uint32_t dy_stride, float* dx, uint32_t dx_stride);
-void launch_identity_fwd(hipStream_t st, uint32_t B, uint32_t D, float scale, float offset, const float* x, uint32_t x_stride,
-                         void* out16, uint32_t out_stride, uint32_t n_pad);
-void launch_identity_bwd(hipStream_t st, uint32_t B, uint32_t D, float scale, const void* dy16, uint32_t dy_stride, float* dx,
+// dL/dx fp32 [B][x_stride] from dL/dy AoS (kernel_one_blob_backward, oneblob.h:116-147)
+template <typename T>
+void launch_oneblob_bwd(hipStream_t st, uint32_t B, uint32_t D, uint32_t n_bins, const float* x, uint32_t x_stride, const T* dy,
+                        uint32_t dy_stride, float* dx, uint32_t dx_stride);
+template <typename T>
+void launch_identity_fwd(hipStream_t st, uint32_t B, uint32_t D, float scale, float offset, const float* x, uint32_t x_stride, T* out,
+                         uint32_t out_stride, uint32_t n_pad);
+template <typename T>
+void launch_identity_bwd(hipStream_t st, uint32_t B, uint32_t D, float scale, const T* dy, uint32_t dy_stride, float* dx,
                          uint32_t dx_stride);
 
 // Composite encodings (composite.hip; reference encodings/composite.h with Concatenation, and
@@ -357,44 +371,27 @@ struct CompTable {
 	uint8_t slot_part[COMP_MAX_INPUTS], slot_col[COMP_MAX_INPUTS];
 };
 // every column of every row that no nested grid's own forward writes (values of the parameter-free
-// parts and all padding, the grids' included): one launch
-void launch_composite_fwd(hipStream_t st, uint32_t B, const float* x, void* out16, const CompTable& t);
+// parts and all padding, the grids' included): one launch; out AoS [B][t.width] of T (_Float16 / float)
+template <typename T>
+void launch_composite_fwd(hipStream_t st, uint32_t B, const float* x, T* out, const CompTable& t);
 // dL/dx fp32 [B][n_in] of the parameter-free parts' columns and zeros in the unread columns (plain
-// stores); dy16 AoS fp16 [B][dy_stride]
-void launch_composite_bwd_input(hipStream_t st, uint32_t B, const float* x, const void* dy16, uint32_t dy_stride, float* dx,
+// stores); dy AoS [B][dy_stride]
+template <typename T>
+void launch_composite_bwd_input(hipStream_t st, uint32_t B, const float* x, const T* dy, uint32_t dy_stride, float* dx,
                                 const CompTable& t);
 
-// ---- fp32-precision encoding modules (Encoding dtype = float32; grid_f32.hip and the float
-// instantiations of the typed kernels in grid.hip, composite.hip, encodings.hip). Tables, encoded rows
-// AoS [B][stride], dL/dy and dL/d(dL/dy) are fp32 and nothing in between is narrowed to fp16. Same
-// arguments as the fp16 launchers above; dL/dy is always AoS rows. ----
+// ---- fp32-precision encoding modules (Encoding dtype = float32): the float forms of the typed
+// launchers above, and in grid_f32.hip the grid forward and parameter backward, which are kernels of
+// their own (the fp16 forward is packed-fp16 arithmetic, the fp16 backward reads three dL/dy layouts).
+// Tables, encoded rows AoS [B][stride], dL/dy and dL/d(dL/dy) are fp32 and nothing in between is
+// narrowed to fp16; dL/dy is always AoS rows. ----
 // only the value columns [0, L * F) of each row are written
-void launch_grid_fwd_f32(hipStream_t st, uint32_t D, uint32_t F, HashType h, uint32_t B, uint32_t L, const float* pos,
-                         uint32_t pos_stride, const float* table32, float* out32, uint32_t out_stride, const LevelInfo* levels,
-                         bool hash_grid, Interp interp, const GridOpts& opts = GridOpts{});
+void launch_grid_fwd_f32(hipStream_t st, const GridCall& g, uint32_t B, const float* pos, uint32_t pos_stride, const float* table32,
+                         float* out32, uint32_t out_stride);
 // LDS-privatised backward: items with all F features (slabs in parameter order), partial [n_chunks][partial_stride]
-void launch_grid_bwd_f32(hipStream_t st, uint32_t D, uint32_t F, HashType h, uint32_t B, const float* pos, uint32_t pos_stride,
-                         const float* dLdy32, uint32_t dy_stride, const GridSlice* slices, uint32_t n_slices, uint32_t n_chunks,
-                         float* partial, uint32_t partial_stride, const LevelInfo* levels, bool hash_grid, Interp interp,
-                         const GridOpts& opts = GridOpts{});
-void launch_grid_bwd_input_f32(hipStream_t st, uint32_t D, uint32_t F, HashType h, uint32_t B, uint32_t L, const float* pos,
-                               uint32_t pos_stride, const float* table32, const float* dLdy32, uint32_t dy_stride, float* dx,
-                               uint32_t dx_stride, const LevelInfo* levels, bool hash_grid, Interp interp, const GridOpts& opts = GridOpts{});
-void launch_grid_bwd_bwd_f32(hipStream_t st, uint32_t D, uint32_t F, HashType h, uint32_t B, uint32_t L, const float* pos,
-                             uint32_t pos_stride, const float* table32, const float* dL_ddLdx, const float* dLdy32, uint32_t dy_stride,
-                             float* grad32, float* dLddLdy32, uint32_t ddy_stride, float* dx, const LevelInfo* levels, bool hash_grid,
-                             Interp interp, const GridOpts& opts = GridOpts{});
-void launch_oneblob_fwd_f32(hipStream_t st, uint32_t B, uint32_t D, uint32_t n_bins, const float* x, uint32_t x_stride, float* out32,
-                            uint32_t out_stride, uint32_t n_pad);
-void launch_oneblob_bwd_f32(hipStream_t st, uint32_t B, uint32_t D, uint32_t n_bins, const float* x, uint32_t x_stride,
-                            const float* dy32, uint32_t dy_stride, float* dx, uint32_t dx_stride);
-void launch_identity_fwd_f32(hipStream_t st, uint32_t B, uint32_t D, float scale, float offset, const float* x, uint32_t x_stride,
-                             float* out32, uint32_t out_stride, uint32_t n_pad);
-void launch_identity_bwd_f32(hipStream_t st, uint32_t B, uint32_t D, float scale, const float* dy32, uint32_t dy_stride, float* dx,
-                             uint32_t dx_stride);
-void launch_composite_fwd_f32(hipStream_t st, uint32_t B, const float* x, float* out32, const CompTable& t);
-void launch_composite_bwd_input_f32(hipStream_t st, uint32_t B, const float* x, const float* dy32, uint32_t dy_stride, float* dx,
-                                    const CompTable& t);
+void launch_grid_bwd_f32(hipStream_t st, const GridCall& g, uint32_t B, const float* pos, uint32_t pos_stride, const float* dLdy32,
+                         uint32_t dy_stride, const GridSlice* slices, uint32_t n_slices, uint32_t n_chunks, float* partial,
+                         uint32_t partial_stride);
 
 void launch_probe_hfma(hipStream_t st, const void* a, const void* b, const void* c, void* out, uint32_t n_pairs);
 // Diagnostic: the config_hash fused (pipelined) kernel with s_memtime phase stamps (prof: [blocks*8][8] u64).

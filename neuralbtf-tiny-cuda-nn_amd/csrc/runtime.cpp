@@ -363,17 +363,15 @@ void GridEncodingHost::backward_items(hipStream_t st, GridBwdBufs& w, uint32_t B
 	w.plan = plan_for(B, reserved);
 	const GridPlan& pl = plans[w.plan];
 	if (!pl.slices.empty()) w.partial.reserve((size_t)n_chunks * n_lds_params * 4);
-	launch_grid_bwd(st, desc.n_pos_dims, desc.n_features_per_level, desc.hash_type, B, pos, pstride, dy, layout, dy_stride,
-	                pl.d_slices.as<GridSlice>(), (uint32_t)pl.slices.size(), n_chunks, w.partial.as<float>(), n_lds_params, dev_levels(),
-	                hash_grid(), desc.interp, ep, opts(), pl.slices.data(), levels.data(), (uint32_t)levels.size(), dy_bound);
+	launch_grid_bwd(st, call(), B, pos, pstride, dy, layout, dy_stride, pl.d_slices.as<GridSlice>(), (uint32_t)pl.slices.size(), n_chunks,
+	                w.partial.as<float>(), n_lds_params, ep, pl.slices.data(), levels.data(), dy_bound);
 }
 
 void GridEncodingHost::backward_bin(hipStream_t st, GridBwdBufs& w, uint32_t B, const float* pos, uint32_t pstride, const void* dy,
                                     int layout, uint32_t dy_stride) const {
 	if (bin_levels.empty() || B == 0) return;
 	const GridBinArgs a = bin_args(w, B);
-	launch_grid_bin(st, desc.n_pos_dims, desc.n_features_per_level, desc.hash_type, B, pos, pstride, dy, layout, dy_stride, dev_levels(),
-	                hash_grid(), desc.interp, a, opts());
+	launch_grid_bin(st, call(), B, pos, pstride, dy, layout, dy_stride, a);
 }
 
 void GridEncodingHost::backward_acc(hipStream_t st, GridBwdBufs& w, uint32_t B, const void* dy, int layout, uint32_t dy_stride,
@@ -384,7 +382,7 @@ void GridEncodingHost::backward_acc(hipStream_t st, GridBwdBufs& w, uint32_t B, 
 		return;
 	}
 	const GridBinArgs a = bin_args(w, B);
-	launch_grid_acc(st, desc.n_pos_dims, desc.n_features_per_level, B, dy, layout, dy_stride, dev_levels(), a, grad32, adam);
+	launch_grid_acc(st, call(), B, dy, layout, dy_stride, a, grad32, adam);
 }
 
 void GridEncodingHost::reduce_items(hipStream_t st, GridBwdBufs& w, float* grad32, GradFinalize fin) const {
@@ -398,25 +396,6 @@ void GridEncodingHost::backward(hipStream_t st, GridBwdBufs& w, uint32_t B, cons
 	backward_bin(st, w, B, pos, pstride, dy, layout, dy_stride);
 	backward_acc(st, w, B, dy, layout, dy_stride, grad32);
 	reduce_items(st, w, grad32);
-}
-
-void GridEncodingHost::forward(hipStream_t st, uint32_t B, const float* pos, uint32_t pos_stride, const void* table16, void* out16,
-                               bool soa, uint32_t out_stride, uint32_t aos_row_cols) const {
-	launch_grid_fwd(st, desc.n_pos_dims, desc.n_features_per_level, desc.hash_type, B, desc.n_levels, pos, pos_stride, table16, out16, soa,
-	                out_stride, dev_levels(), hash_grid(), desc.interp, opts(), aos_row_cols);
-}
-
-void GridEncodingHost::backward_input(hipStream_t st, uint32_t B, const float* pos, uint32_t pos_stride, const void* table16,
-                                      const void* dy16, int dy_layout, uint32_t dy_stride, float* dx, uint32_t dx_stride) const {
-	launch_grid_bwd_input(st, desc.n_pos_dims, desc.n_features_per_level, desc.hash_type, B, desc.n_levels, pos, pos_stride, table16, dy16,
-	                      dy_layout, dy_stride, dx, dx_stride, dev_levels(), hash_grid(), desc.interp, opts());
-}
-
-void GridEncodingHost::backward_backward_input(hipStream_t st, uint32_t B, const float* pos, uint32_t pos_stride, const void* table16,
-                                               const float* dL_ddLdx, const void* dy16, uint32_t dy_stride, float* grad32,
-                                               void* dLddLdy16, uint32_t ddy_stride, float* dx) const {
-	launch_grid_bwd_bwd(st, desc.n_pos_dims, desc.n_features_per_level, desc.hash_type, B, desc.n_levels, pos, pos_stride, table16,
-	                    dL_ddLdx, dy16, dy_stride, grad32, dLddLdy16, ddy_stride, dx, dev_levels(), hash_grid(), desc.interp, opts());
 }
 
 // fp32 modules: every level as LDS items with all F features. A level whose F features fit the LDS
@@ -443,12 +422,6 @@ void GridEncodingHost::build_plan_f32() {
 	TCNN_HIP_CHECK(hipMemcpy(plan_f32.d_slices.p, out.data(), out.size() * sizeof(GridSlice), hipMemcpyHostToDevice));
 }
 
-void GridEncodingHost::forward_f32(hipStream_t st, uint32_t B, const float* pos, uint32_t pos_stride, const float* table32, float* out32,
-                                   uint32_t out_stride) const {
-	launch_grid_fwd_f32(st, desc.n_pos_dims, desc.n_features_per_level, desc.hash_type, B, desc.n_levels, pos, pos_stride, table32, out32,
-	                    out_stride, dev_levels(), hash_grid(), desc.interp, opts());
-}
-
 void GridEncodingHost::backward_f32(hipStream_t st, GridBwdBufs& w, uint32_t B, const float* pos, uint32_t pstride, const float* dy32,
                                     uint32_t dy_stride, float* grad32) const {
 	TCNN_CHECK(!plan_f32.slices.empty(), "GridEncoding: the fp32 backward plan was not built");
@@ -463,23 +436,9 @@ void GridEncodingHost::backward_f32(hipStream_t st, GridBwdBufs& w, uint32_t B, 
 		w.partial.reserve((size_t)n_chunks * n_params * 4);
 		partial = w.partial.as<float>();
 	}
-	launch_grid_bwd_f32(st, desc.n_pos_dims, desc.n_features_per_level, desc.hash_type, B, pos, pstride, dy32, dy_stride,
-	                    plan_f32.d_slices.as<GridSlice>(), (uint32_t)plan_f32.slices.size(), n_chunks, partial, n_params, dev_levels(),
-	                    hash_grid(), desc.interp, opts());
+	launch_grid_bwd_f32(st, call(), B, pos, pstride, dy32, dy_stride, plan_f32.d_slices.as<GridSlice>(), (uint32_t)plan_f32.slices.size(),
+	                    n_chunks, partial, n_params);
 	if (n_chunks > 1) launch_grid_slab_reduce(st, partial, n_chunks, n_params, n_params, grad32, nullptr);
-}
-
-void GridEncodingHost::backward_input_f32(hipStream_t st, uint32_t B, const float* pos, uint32_t pos_stride, const float* table32,
-                                          const float* dy32, uint32_t dy_stride, float* dx, uint32_t dx_stride) const {
-	launch_grid_bwd_input_f32(st, desc.n_pos_dims, desc.n_features_per_level, desc.hash_type, B, desc.n_levels, pos, pos_stride, table32,
-	                          dy32, dy_stride, dx, dx_stride, dev_levels(), hash_grid(), desc.interp, opts());
-}
-
-void GridEncodingHost::backward_backward_input_f32(hipStream_t st, uint32_t B, const float* pos, uint32_t pos_stride, const float* table32,
-                                                   const float* dL_ddLdx, const float* dy32, uint32_t dy_stride, float* grad32,
-                                                   float* dLddLdy32, uint32_t ddy_stride, float* dx) const {
-	launch_grid_bwd_bwd_f32(st, desc.n_pos_dims, desc.n_features_per_level, desc.hash_type, B, desc.n_levels, pos, pos_stride, table32,
-	                        dL_ddLdx, dy32, dy_stride, grad32, dLddLdy32, ddy_stride, dx, dev_levels(), hash_grid(), desc.interp, opts());
 }
 
 static const char* grid_type_str(GridType t) { return t == GridType::Hash ? "Hash" : t == GridType::Dense ? "Dense" : "Tiled"; }
@@ -788,51 +747,49 @@ json EncodingHost::hyperparams() const {
 	return {{"otype", "Composite"}, {"nested", nested}};  // composite.h:437-447
 }
 
+// fn(T{}) with T the element type of an encoding's precision: one body for the fp16 and the fp32 module
+template <typename Fn>
+static void with_precision(bool f32, Fn&& fn) {
+	if (f32) fn(float{});
+	else fn(_Float16{});
+}
+
 void EncodingHost::Part::forward(hipStream_t st, uint32_t B, const float* x, uint32_t x_stride, const void* params16, void* out16,
                                  uint32_t stride, bool alone) const {
-	if (f32) {  // the same part at fp32: fp32 parameters and rows
-		float* o = (float*)out16 + out_col;
-		if (kind == COMP_ONEBLOB) return launch_oneblob_fwd_f32(st, B, n_in, p0, x + in_col, x_stride, o, stride, width - n_values);
-		if (kind == COMP_IDENTITY) return launch_identity_fwd_f32(st, B, n_in, f0, f1, x + in_col, x_stride, o, stride, width - n_values);
+	with_precision(f32, [&](auto zero) {
+		using T = decltype(zero);
+		T* out = (T*)out16 + out_col;
+		if (kind == COMP_ONEBLOB) return launch_oneblob_fwd(st, B, n_in, p0, x + in_col, x_stride, out, stride, width - n_values);
+		if (kind == COMP_IDENTITY) return launch_identity_fwd(st, B, n_in, f0, f1, x + in_col, x_stride, out, stride, width - n_values);
 		TCNN_CHECK(kind == COMP_GRID, "this encoding has no kernel of its own");
 		TCNN_CHECK(params16, "grid forward needs the grid parameters");
-		if (alone && width > n_values) TCNN_HIP_CHECK(hipMemsetAsync(out16, 0, (size_t)B * stride * 4, st));
-		return grid->forward_f32(st, B, x + in_col, x_stride, (const float*)params16 + param_offset, o, stride);
-	}
-	_Float16* out = (_Float16*)out16 + out_col;
-	if (kind == COMP_ONEBLOB) return launch_oneblob_fwd(st, B, n_in, p0, x + in_col, x_stride, out, stride, width - n_values);
-	if (kind == COMP_IDENTITY) return launch_identity_fwd(st, B, n_in, f0, f1, x + in_col, x_stride, out, stride, width - n_values);
-	TCNN_CHECK(kind == COMP_GRID, "this encoding has no kernel of its own");
-	TCNN_CHECK(params16, "grid forward needs the grid parameters");
-	if (alone && width > n_values) TCNN_HIP_CHECK(hipMemsetAsync(out16, 0, (size_t)B * stride * 2, st));
-	grid->forward(st, B, x + in_col, x_stride, (const _Float16*)params16 + param_offset, out, false, stride, alone ? 0u : n_values);
+		if (alone && width > n_values) TCNN_HIP_CHECK(hipMemsetAsync(out16, 0, (size_t)B * stride * sizeof(T), st));
+		const T* table = (const T*)params16 + param_offset;
+		// the fp32 forward writes its value columns only; the fp16 one whole rows, or the part's columns
+		if constexpr (sizeof(T) == 4) grid->forward_f32(st, B, x + in_col, x_stride, table, out, stride);
+		else grid->forward(st, B, x + in_col, x_stride, table, out, false, stride, alone ? 0u : n_values);
+	});
 }
 
 void EncodingHost::Part::backward_input(hipStream_t st, uint32_t B, const float* x, uint32_t x_stride, const void* params16,
                                         const void* dy16, int dy_layout, uint32_t stride, float* dx) const {
-	if (f32) {
-		const float* g = (const float*)dy16 + out_col;
-		TCNN_CHECK(dy_layout == 2, "an fp32 encoding reads dL/d(encoding) as AoS rows");
-		if (kind == COMP_ONEBLOB) return launch_oneblob_bwd_f32(st, B, n_in, p0, x + in_col, x_stride, g, stride, dx + in_col, x_stride);
-		if (kind == COMP_IDENTITY) return launch_identity_bwd_f32(st, B, n_in, f0, g, stride, dx + in_col, x_stride);
+	TCNN_CHECK(!f32 || dy_layout == 2, "an fp32 encoding reads dL/d(encoding) as AoS rows");
+	with_precision(f32, [&](auto zero) {
+		using T = decltype(zero);
+		const T* dy = (const T*)dy16 + out_col;
+		if (kind == COMP_ONEBLOB) return launch_oneblob_bwd(st, B, n_in, p0, x + in_col, x_stride, dy, stride, dx + in_col, x_stride);
+		if (kind == COMP_IDENTITY) return launch_identity_bwd(st, B, n_in, f0, dy, stride, dx + in_col, x_stride);
 		TCNN_CHECK(kind == COMP_GRID, "this encoding has no kernel of its own");
 		TCNN_CHECK(params16, "grid backward_input needs the grid parameters");
-		return grid->backward_input_f32(st, B, x + in_col, x_stride, (const float*)params16 + param_offset, g, stride, dx + in_col, x_stride);
-	}
-	const _Float16* dy = (const _Float16*)dy16 + out_col;
-	if (kind == COMP_ONEBLOB) return launch_oneblob_bwd(st, B, n_in, p0, x + in_col, x_stride, dy, stride, dx + in_col, x_stride);
-	if (kind == COMP_IDENTITY) return launch_identity_bwd(st, B, n_in, f0, dy, stride, dx + in_col, x_stride);
-	TCNN_CHECK(kind == COMP_GRID, "this encoding has no kernel of its own");
-	TCNN_CHECK(params16, "grid backward_input needs the grid parameters");
-	grid->backward_input(st, B, x + in_col, x_stride, (const _Float16*)params16 + param_offset, dy, dy_layout, stride, dx + in_col, x_stride);
+		grid->backward_input(st, B, x + in_col, x_stride, (const T*)params16 + param_offset, dy, dy_layout, stride, dx + in_col, x_stride);
+	});
 }
 
 void EncodingHost::forward_aos(hipStream_t st, uint32_t B, const float* x, const void* params16, void* out16) const {
 	const uint32_t W = padded_output_width();
 	if (const Part* p = lone_part()) return p->forward(st, B, x, n_dims, params16, out16, W, true);
 	// one launch for every parameter-free value and all padding; each grid its own column slice
-	if (f32) launch_composite_fwd_f32(st, B, x, (float*)out16, table);
-	else launch_composite_fwd(st, B, x, out16, table);
+	with_precision(f32, [&](auto zero) { launch_composite_fwd(st, B, x, (decltype(zero)*)out16, table); });
 	for (const Part& p : parts)
 		if (p.grid) p.forward(st, B, x, n_dims, params16, out16, W, false);
 }
@@ -842,8 +799,7 @@ void EncodingHost::backward_input(hipStream_t st, uint32_t B, const float* x, co
 	const uint32_t W = padded_output_width();
 	TCNN_CHECK(dy_layout == 2 || lone_grid(), "backward_input reads dL/d(encoding) as AoS rows");
 	if (const Part* p = lone_part()) return p->backward_input(st, B, x, n_dims, params16, dy16, dy_layout, W, dx);
-	if (f32) launch_composite_bwd_input_f32(st, B, x, (const float*)dy16, W, dx, table);
-	else launch_composite_bwd_input(st, B, x, dy16, W, dx, table);
+	with_precision(f32, [&](auto zero) { launch_composite_bwd_input(st, B, x, (const decltype(zero)*)dy16, W, dx, table); });
 	for (const Part& p : parts)
 		if (p.grid) p.backward_input(st, B, x, n_dims, params16, dy16, 2, W, dx);
 }
@@ -986,9 +942,8 @@ void NetworkHost::fused_forward(hipStream_t st, StepWorkspace& ws, uint32_t B, c
 		ws.wimage_valid = false;  // packed from these parameters, which need not be the trainer's
 		use_image = true;
 	}
-	launch_fused_fwd(st, mlp.width, IN, mlp.n_hidden_layers, grid->desc.n_pos_dims, grid->desc.hash_type, mlp.activation, B,
-	                 use_image ? ws.wimage.p : nullptr, params16, eparams, pos, grid->dev_levels(), grid->hash_grid(), grid->desc.interp,
-	                 grid->inrange_index_ok && grid->desc.interp == Interp::Linear && !sw.no_inrange_index, enc_soa, out16);
+	launch_fused_fwd(st, grid->call(), mlp.width, IN, mlp.n_hidden_layers, mlp.activation, B, use_image ? ws.wimage.p : nullptr, params16,
+	                 eparams, pos, enc_soa, out16);
 }
 
 int NetworkHost::backward_engine_keep(bool with_dinput) const {
@@ -1062,12 +1017,10 @@ void NetworkHost::fused_kernel(hipStream_t st, StepWorkspace& ws, uint32_t B, co
 		ws.wimage_valid = false;
 		use_image = true;
 	}
-	launch_fused_train(st, mlp.width, mlp.n_input, mlp.n_hidden_layers, grid->desc.n_pos_dims, grid->desc.hash_type,
-	                   mlp.activation, B, dims, loss_scale, params16, enc_params(params16), pos, target, out16, ws.dLdenc.p,
-	                   ws.wgrad_partial.as<float>(), ws.loss_partial.as<float>(), grid->dev_levels(), grid->hash_grid(),
-	                   grid->desc.interp, nb, dout16, use_image ? ws.wimage.p : nullptr, loss_type,
-	                   grid->inrange_index_ok && grid->desc.interp == Interp::Linear && !sw.no_inrange_index, enc_soa,
-	                   dout16 ? ext_dout_scale : 1.0f, ws.dy_bound_live ? ws.dy_bound.as<float>() : nullptr);
+	launch_fused_train(st, grid->call(), mlp.width, mlp.n_input, mlp.n_hidden_layers, mlp.activation, B, dims, loss_scale, params16,
+	                   enc_params(params16), pos, target, out16, ws.dLdenc.p, ws.wgrad_partial.as<float>(), ws.loss_partial.as<float>(), nb,
+	                   dout16, use_image ? ws.wimage.p : nullptr, loss_type, enc_soa, dout16 ? ext_dout_scale : 1.0f,
+	                   ws.dy_bound_live ? ws.dy_bound.as<float>() : nullptr);
 }
 
 void NetworkHost::grid_backward(hipStream_t st, StepWorkspace& ws, uint32_t B, const float* pos, GridBwdEpilogue* ep) {
@@ -1138,12 +1091,8 @@ void NetworkHost::fwd_bwd_tile(hipStream_t st, StepWorkspace& ws, uint32_t B, co
 	                       (dout16 || loss_type <= LOSS_L2) &&  // the in-kernel encode is instantiated for the default kernel only
 	                       tile_train_genc_ok(W, IN, NH, mlp.activation, B, grid->desc.hash_type);
 	if (in_kernel) {
-		genc.pos = pos;
-		genc.table16 = eparams;
-		genc.levels = grid->dev_levels();
-		genc.hash = grid->desc.hash_type;
-		genc.hash_grid = grid->hash_grid() ? 1u : 0u;
-		genc.inrange = grid->opts().inrange_index;
+		const GridCall gc = grid->call();
+		genc = TileGridEnc{pos, eparams, gc.levels, gc.hash, gc.hash_grid ? 1u : 0u, gc.opts.inrange_index};
 	} else if (!enc_aos) {
 		ws.enc16.reserve((size_t)B * IN * 2);
 		enc->forward_aos(st, B, pos, eparams, ws.enc16.p);

@@ -129,6 +129,10 @@ struct GridEncodingHost {
 		o.inrange_index = (inrange_index_ok && desc.interp == Interp::Linear && !sw.no_inrange_index) ? 1u : 0u;
 		return o;
 	}
+	// this grid as every grid launcher takes it (kernels.h)
+	GridCall call() const {
+		return GridCall{desc.n_pos_dims, desc.n_features_per_level, desc.n_levels, desc.hash_type, hash_grid(), desc.interp, dev_levels(), opts()};
+	}
 	// the slabs' element order under a plan; nullptr when it is the parameter order (every LDS item holds
 	// all F features of its entries: the readers then index the slabs directly, no dependent map load)
 	const GridSlabMap* slab_map(int plan) const { return plans[plan].identity ? nullptr : d_slab_map.as<GridSlabMap>(); }
@@ -178,15 +182,22 @@ struct GridEncodingHost {
 	void reduce_items(hipStream_t st, GridBwdBufs& w, float* grad32, GradFinalize fin = {}) const;
 	void backward(hipStream_t st, GridBwdBufs& w, uint32_t B, const float* pos, uint32_t pstride, const void* dy, int layout,
 	              uint32_t dy_stride, float* grad32) const;
-	// launch_grid_fwd / launch_grid_bwd_input / launch_grid_bwd_bwd (kernels.h) with this grid's
-	// shape, level table and options filled in
+	// launch_grid_fwd / launch_grid_bwd_input / launch_grid_bwd_bwd (kernels.h) on this grid (call()).
+	// T: the module's precision (_Float16, or float for an fp32 encoding module)
 	void forward(hipStream_t st, uint32_t B, const float* pos, uint32_t pos_stride, const void* table16, void* out16, bool soa,
-	             uint32_t out_stride, uint32_t aos_row_cols = 0) const;
-	void backward_input(hipStream_t st, uint32_t B, const float* pos, uint32_t pos_stride, const void* table16, const void* dy16,
-	                    int dy_layout, uint32_t dy_stride, float* dx, uint32_t dx_stride) const;
-	void backward_backward_input(hipStream_t st, uint32_t B, const float* pos, uint32_t pos_stride, const void* table16,
-	                             const float* dL_ddLdx, const void* dy16, uint32_t dy_stride, float* grad32, void* dLddLdy16,
-	                             uint32_t ddy_stride, float* dx) const;
+	             uint32_t out_stride, uint32_t aos_row_cols = 0) const {
+		launch_grid_fwd(st, call(), B, pos, pos_stride, table16, out16, soa, out_stride, aos_row_cols);
+	}
+	template <typename T>
+	void backward_input(hipStream_t st, uint32_t B, const float* pos, uint32_t pos_stride, const T* table, const T* dy, int dy_layout,
+	                    uint32_t dy_stride, float* dx, uint32_t dx_stride) const {
+		launch_grid_bwd_input(st, call(), B, pos, pos_stride, table, dy, dy_layout, dy_stride, dx, dx_stride);
+	}
+	template <typename T>
+	void backward_backward_input(hipStream_t st, uint32_t B, const float* pos, uint32_t pos_stride, const T* table, const float* dL_ddLdx,
+	                             const T* dy, uint32_t dy_stride, float* grad32, T* dLddLdy, uint32_t ddy_stride, float* dx) const {
+		launch_grid_bwd_bwd(st, call(), B, pos, pos_stride, table, dL_ddLdx, dy, dy_stride, grad32, dLddLdy, ddy_stride, dx);
+	}
 
 	// ---- fp32 precision (an fp32 encoding module: fp32 table, AoS fp32 rows and dL/dy; grid_f32.hip) ----
 	// The backward's work plan: EVERY level as LDS items holding all F features -- whole levels, or entry
@@ -200,15 +211,12 @@ struct GridEncodingHost {
 		return std::max(1u, std::min(std::min(std::max(256u / n_items, 1u), 32u), B / 8192));
 	}
 	void forward_f32(hipStream_t st, uint32_t B, const float* pos, uint32_t pos_stride, const float* table32, float* out32,
-	                 uint32_t out_stride) const;
+	                 uint32_t out_stride) const {
+		launch_grid_fwd_f32(st, call(), B, pos, pos_stride, table32, out32, out_stride);
+	}
 	// the fp32 gradient of every grid parameter into grad32 [n_params], bit-reproducible
 	void backward_f32(hipStream_t st, GridBwdBufs& w, uint32_t B, const float* pos, uint32_t pstride, const float* dy32, uint32_t dy_stride,
 	                  float* grad32) const;
-	void backward_input_f32(hipStream_t st, uint32_t B, const float* pos, uint32_t pos_stride, const float* table32, const float* dy32,
-	                        uint32_t dy_stride, float* dx, uint32_t dx_stride) const;
-	void backward_backward_input_f32(hipStream_t st, uint32_t B, const float* pos, uint32_t pos_stride, const float* table32,
-	                                 const float* dL_ddLdx, const float* dy32, uint32_t dy_stride, float* grad32, float* dLddLdy32,
-	                                 uint32_t ddy_stride, float* dx) const;
 };
 
 // ---- fully fused MLP shape (reference networks/fully_fused_mlp.h) ----

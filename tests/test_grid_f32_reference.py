@@ -2,8 +2,8 @@
 
 A vectorised float64 numpy restatement of the multiresolution grid for any D: positions as the
 single-rounded fmaf (float64(x) * float64(scale) + 0.5 rounded once to float32, as tests/test_fixtures.py
-argues), floor and fraction (exact in float32), the corner indices of dense, tiled and coherent-prime
-hashed levels (reference common_device.h:690-707), and float64 weights, interpolation sums and gradient
+argues), floor and fraction (exact in float32), the corner indices of dense, tiled and hashed levels under
+each of the three hashes (reference common_device.h:645-707), and float64 weights, interpolation sums and gradient
 sums. tests/test_gpu_encoding_f32.py checks the fp32 kernels against it; here it is checked against the
 oracle (the reference's fp16 arithmetic) on fp16-representable tables, where the two may differ only by
 the fp16 roundings the oracle models.
@@ -13,7 +13,13 @@ import pytest
 
 from oracle import oracle as O
 
-PRIMES = (1, 2654435761, 805459861, 3674653429)  # CoherentPrime (common_device.h:650-663)
+# the three hashes' per-dimension factors (prime_hash, coherent_prime_hash, reversed_prime_hash,
+# common_device.h:645-661; csrc/grid_device.h hash_prime), keyed by the oracle's hash_type
+PRIMES = {
+    0: (1958374283, 2654435761, 805459861, 3674653429),  # Prime
+    1: (1, 2654435761, 805459861, 3674653429),           # CoherentPrime
+    2: (2165219737, 1434869437, 2097192037, 3674653429),  # ReversedPrime
+}
 M32 = np.uint64(0xFFFFFFFF)
 
 GRID2_L8 = {"otype": "HashGrid", "n_levels": 8, "n_features_per_level": 2, "log2_hashmap_size": 12, "base_resolution": 8,
@@ -25,6 +31,9 @@ DENSE3_F1 = {"otype": "DenseGrid", "n_levels": 3, "n_features_per_level": 1, "ba
 TILED4_F8 = {"otype": "TiledGrid", "n_levels": 2, "n_features_per_level": 8, "base_resolution": 3, "per_level_scale": 2.0}
 # (name, D, encoding): dense + hashed levels, wide features, Smoothstep on a dense grid, a tiled 4-D grid
 GRID_CASES = [("grid2_l8", 2, GRID2_L8), ("grid3_f4", 3, GRID3_F4), ("dense3_f1_smooth", 3, DENSE3_F1), ("tiled4_f8", 4, TILED4_F8)]
+# the other two hashes, pinned to the oracle below (CPU only: tests/test_gpu_grid_dispatch.py runs them on the GPU)
+HASH_CASES = [(f"{name}_{h.lower()}", D, dict(enc, hash=h)) for name, D, enc in GRID_CASES[:2] for h in ("Prime", "ReversedPrime")]
+PIN_CASES = GRID_CASES + HASH_CASES
 
 
 def level_size(g, l):
@@ -44,10 +53,9 @@ def grid_index(g, l, pg):
         index = (index + pg[:, d] * np.uint64(stride)) & M32
         stride = (stride * res) & 0xFFFFFFFF
     if g.grid_type == 0 and size < stride:
-        assert g.hash_type == 1, "the reference restates the coherent-prime hash only"
         index = np.zeros(pg.shape[0], np.uint64)
         for d in range(D):
-            index ^= (pg[:, d] * np.uint64(PRIMES[d])) & M32
+            index ^= (pg[:, d] * np.uint64(PRIMES[int(g.hash_type)][d])) & M32
     return (index % np.uint64(size)).astype(np.int64)
 
 
@@ -182,7 +190,7 @@ def make_inputs(g, B, seed):
 # ---------------------------------------------------------------------------------------------
 # the reference against the oracle
 # ---------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name,D,enc", GRID_CASES, ids=[c[0] for c in GRID_CASES])
+@pytest.mark.parametrize("name,D,enc", PIN_CASES, ids=[c[0] for c in PIN_CASES])
 def test_reference_forward_matches_oracle(name, D, enc):
     """On an fp16-representable table the oracle (the reference's fp16 arithmetic) and the float64
     restatement touch the same entries and differ only by the oracle's fp16 roundings: each of the 2^D
@@ -209,7 +217,7 @@ def test_reference_forward_matches_oracle(name, D, enc):
     assert np.abs(got - ref).max() > 0  # the comparison is not vacuous: fp16 arithmetic does differ
 
 
-@pytest.mark.parametrize("name,D,enc", GRID_CASES, ids=[c[0] for c in GRID_CASES])
+@pytest.mark.parametrize("name,D,enc", PIN_CASES, ids=[c[0] for c in PIN_CASES])
 def test_reference_gradient_matches_oracle(name, D, enc):
     """The oracle's backward adds fp32(w16 * dy16) sequentially in fp32: against the float64 sums it is
     off by the fp16 rounding of each weight (2^-11 |w dy|, or 2^-25 |dy| in the subnormals) and by its
