@@ -174,6 +174,11 @@ tcnn_trainer_context* tcnn_trainer_forward(tcnn_trainer* t, void* stream, uint32
  * output stays the unperturbed one. */
 tcnn_trainer_context* tcnn_trainer_forward_perturbed(tcnn_trainer* t, void* stream, uint32_t n, const float* input, const float* target,
                                                      const float* data_pdf, const float* perturbation, int prepare_input_gradients);
+/* Trainer::forward with use_inference_params (trainer.h:97-112): the output and the loss at the optimizer's
+ * custom weights (tcnn_trainer_params_inference). Such a context serves output and loss only:
+ * tcnn_trainer_backward refuses it (gradients are taken at the training parameters). */
+tcnn_trainer_context* tcnn_trainer_forward_inference_params(tcnn_trainer* t, void* stream, uint32_t n, const float* input,
+                                                            const float* target, const float* data_pdf, const void* external_dL_dy);
 /* gradient_mode: GradientMode (common.h) -- 0 Overwrite, 1 Accumulate, 2 Ignore (dL/dinput only; the
  * parameter gradients are left as they are) */
 int tcnn_trainer_backward(tcnn_trainer* t, void* stream, const tcnn_trainer_context* ctx, uint32_t n, const float* input,
@@ -255,11 +260,28 @@ uint64_t tcnn_trainer_n_network_params(const tcnn_trainer* t); /* MLP part; grid
  * gradient sum the kernels produce (what a data-parallel all-reduce exchanges). */
 float* tcnn_trainer_params_fp32(tcnn_trainer* t);
 void* tcnn_trainer_params(tcnn_trainer* t);
+/* Trainer::params_inference() (trainer.h:234-236, 330-335): the fp16 parameters tcnn_trainer_inference and
+ * the snapshot's params_binary read -- the optimizer's custom weights (Ema: the averaged weights,
+ * Lookahead: the slow weights), else the training parameters. */
+void* tcnn_trainer_params_inference(tcnn_trainer* t);
 void* tcnn_trainer_param_gradients(tcnn_trainer* t);
 float* tcnn_trainer_gradients_fp32(tcnn_trainer* t);
 /* Adam state buffers (adam.h:128-148): first / second moments fp32 and per-parameter step counts
  * uint32, [n_params] each (device pointers owned by the trainer). */
 int tcnn_trainer_optimizer_state(tcnn_trainer* t, float** first_moments, float** second_moments, uint32_t** steps);
+/* A state buffer of a stacked optimizer by name, outermost level first: "weights_ema" (fp16), "tmp" (fp32,
+ * Ema with full_precision), "weights_lookahead" (fp16), "averaged_gradients" (fp32), "averaged_gradients_half"
+ * (fp16); [n_params] each. *ptr = NULL when the optimizer has no such buffer. */
+int tcnn_trainer_optimizer_buffer(tcnn_trainer* t, const char* name, void** ptr, uint32_t* elem_bytes);
+/* Optimizer::learning_rate() / set_learning_rate() of the outermost optimizer (an ExponentialDecay reports
+ * base x factor and stores value / factor, exponential_decay.h:73-80). */
+int tcnn_trainer_learning_rate(const tcnn_trainer* t, float* learning_rate);
+/* Engine diagnostics: how training_step(run_optimizer = 1) schedules the optimizer. "adam": plain Adam, inside
+ * the engine's step; "inline": Adam wrapped only in ExponentialDecay / Ema keeps that schedule (the learning rate
+ * is set on the host before it, one EMA launch follows); "staged": the gradient pass of run_optimizer = 0, then
+ * the optimizer tree on the gradient buffers (SGD, Lookahead, Batched). */
+const char* tcnn_trainer_optimizer_schedule(const tcnn_trainer* t);
+int tcnn_trainer_set_learning_rate(tcnn_trainer* t, float learning_rate);
 /* Data-parallel support: Adam reads grad_fp32 * grad_scale (set 1/N after a sum all-reduce). */
 int tcnn_trainer_set_gradient_scale(tcnn_trainer* t, float scale);
 /* The loss scale training_step / forward / optimizer_step use -- the reference's loss_scale argument of
@@ -289,9 +311,11 @@ int tcnn_trainer_deserialize(tcnn_trainer* t, const void* buf, uint64_t size);
 int tcnn_trainer_serialize_json(tcnn_trainer* t, int with_optimizer, char* buf, uint64_t capacity, uint64_t* size);
 uint32_t tcnn_trainer_optimizer_step_count(const tcnn_trainer* t);
 /* Trainer::update_hyperparams(json) (trainer.h:213-216): {"optimizer": {...}} fields update Adam
- * (adam.h:235-283: learning_rate, betas, epsilon, l2_reg, ...). */
+ * (adam.h:235-283: learning_rate, betas, epsilon, l2_reg, ...); with a stacked optimizer each level takes
+ * its own keys and passes "nested" down. */
 int tcnn_trainer_update_hyperparams(tcnn_trainer* t, const char* params_json);
-/* {"optimizer": Adam hyperparams, "loss": {"otype"}} as JSON; valid until the next call on this thread. */
+/* {"optimizer": the optimizer's hyperparams (its "nested" tree included), "loss": {"otype"}} as JSON; valid
+ * until the next call on this thread. */
 const char* tcnn_trainer_hyperparams(tcnn_trainer* t);
 /* Trainer::initialize_params (trainer.h:68-87): re-seed pcg32{seed_seq{seed}[0]}, re-initialise every
  * parameter, zero the optimizer state and its step counter. */

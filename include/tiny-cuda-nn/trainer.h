@@ -103,7 +103,11 @@ public:
 	                                        bool use_inference_params = false, bool prepare_input_gradients = false,
 	                                        const GPUMatrixDynamic<COMPUTE_T>* external_dL_dy = nullptr) {
 		(void)loss_scale;  // the engine's default_loss_scale<__half>() (common.h:232)
-		(void)use_inference_params;
+		// honoured for a forward that no backward follows (output and loss at params_inference()); without
+		// custom weights the two parameter sets are one
+		const bool on_inference_params = use_inference_params && params_inference() != params();
+		if (on_inference_params && (prepare_input_gradients || m_perturbation_sigma > 0))
+			throw std::runtime_error{"Trainer::forward: use_inference_params serves output and loss only (no input gradients, no perturbation)"};
 		const uint32_t n = input.n();
 		CHECK_THROW(input.m() == m_model->input_width());
 		CHECK_THROW(input.layout() == CM && input.is_contiguous());
@@ -127,7 +131,10 @@ public:
 			m_perturbation.enlarge(n_el);
 			generate_random_logistic(stream, m_rng, n_el, m_perturbation.data(), 0.0f, m_perturbation_sigma);
 		}
-		if (m_perturbation_sigma > 0 && !external_dL_dy) {
+		if (on_inference_params) {
+			ctx->h = tcnn_trainer_forward_inference_params(m_h, stream, n, in, external_dL_dy ? nullptr : target.data(),
+			                                               data_pdf ? data_pdf->data() : nullptr, external_dL_dy ? external_dL_dy->data() : nullptr);
+		} else if (m_perturbation_sigma > 0 && !external_dL_dy) {
 			ctx->h = tcnn_trainer_forward_perturbed(m_h, stream, n, in, target.data(), data_pdf ? data_pdf->data() : nullptr,
 			                                        m_perturbation.data(), prepare_input_gradients ? 1 : 0);
 		} else {
@@ -151,7 +158,7 @@ public:
 	// trainer.h:146-153: parameter gradients (Overwrite or Accumulate) and optionally dL/dinput
 	void backward(hipStream_t stream, const ForwardContext& ctx, const GPUMatrixDynamic<T>& input, GPUMatrixDynamic<T>* dL_dinput = nullptr,
 	              bool use_inference_params = false, GradientMode param_gradients_mode = GradientMode::Overwrite) {
-		(void)use_inference_params;
+		refuse_inference_params_backward(use_inference_params, "backward");
 		if (!ctx.h || ctx.owner != this) throw std::runtime_error{"Trainer::backward: the context was not made by this trainer's forward()"};
 		if (dL_dinput) CHECK_THROW(dL_dinput->m() == m_model->input_width() && dL_dinput->n() == input.n() && dL_dinput->layout() == CM);
 		const int mode = param_gradients_mode == GradientMode::Overwrite ? 0 : param_gradients_mode == GradientMode::Accumulate ? 1 : 2;
@@ -190,7 +197,7 @@ public:
 	                                              GPUMatrixDynamic<T>* dL_dinput = nullptr, bool use_inference_params = false,
 	                                              GradientMode param_gradients_mode = GradientMode::Overwrite,
 	                                              const GPUMatrixDynamic<COMPUTE_T>* external_dL_dy = nullptr) {
-		(void)use_inference_params;
+		refuse_inference_params_backward(use_inference_params, "training_step");
 		CHECK_THROW(input.m() == m_model->input_width());
 		CHECK_THROW(input.n() % BATCH_SIZE_GRANULARITY == 0);
 		CHECK_THROW(input.layout() == CM && input.is_contiguous());
@@ -263,7 +270,8 @@ public:
 	// parameter buffers (trainer.h:226-240, 322-336): device pointers owned by the trainer
 	float* params_full_precision() const { return tcnn_trainer_params_fp32(m_h); }
 	PARAMS_T* params() const { return (PARAMS_T*)tcnn_trainer_params(m_h); }
-	PARAMS_T* params_inference() const { return params(); }
+	// trainer.h:234-236, 330-335: the optimizer's custom weights (Ema, Lookahead), else params()
+	PARAMS_T* params_inference() const { return (PARAMS_T*)tcnn_trainer_params_inference(m_h); }
 	PARAMS_T* param_gradients() const { return (PARAMS_T*)tcnn_trainer_param_gradients(m_h); }
 	size_t n_params() const { return (size_t)tcnn_trainer_n_params(m_h); }
 
@@ -327,6 +335,13 @@ public:
 	float perturbation_sigma() const { return m_perturbation_sigma; }
 
 private:
+	// the engine takes gradients at the training parameters: with custom weights a backward on them is refused
+	void refuse_inference_params_backward(bool use_inference_params, const char* what) const {
+		if (use_inference_params && params_inference() != params())
+			throw std::runtime_error{std::string{"Trainer::"} + what + ": use_inference_params is honoured by inference and by a forward "
+			                         "without a backward only; the optimizer has custom weights and gradients are taken at the training parameters"};
+	}
+
 	// trainer.h:52-55, 68-87: the trainer's pcg32{seed_seq{seed}[0]} after the parameter initialisation
 	// drew its n_params uniforms (generate_random_uniform advances by n_elements, random.h:64) -- the
 	// engine initialises from the same seed, so this is the state the reference's m_rng has when the

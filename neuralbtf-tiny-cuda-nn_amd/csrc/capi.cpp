@@ -559,6 +559,16 @@ tcnn_trainer_context* tcnn_trainer_forward_perturbed(tcnn_trainer* t, void* stre
 	});
 	return rc == 0 ? r : nullptr;
 }
+tcnn_trainer_context* tcnn_trainer_forward_inference_params(tcnn_trainer* t, void* stream, uint32_t n, const float* in, const float* target,
+                                                            const float* pdf, const void* ext) {
+	tcnn_trainer_context* r = nullptr;
+	const int rc = guard([&] {
+		TCNN_CHECK(n > 0, "forward: empty batch");
+		auto c = t->t->forward((hipStream_t)stream, n, in, target, pdf, ext, false, nullptr, true);
+		r = new tcnn_trainer_context{std::move(c)};
+	});
+	return rc == 0 ? r : nullptr;
+}
 int tcnn_trainer_backward(tcnn_trainer* t, void* stream, const tcnn_trainer_context* ctx, uint32_t n, const float* in, float* dL_din,
                           int gradient_mode) {
 	return guard([&] {
@@ -601,14 +611,23 @@ tcnn_dp_comm* tcnn_dp_comm_create(const void* id, int nranks, int rank) {
 }
 void tcnn_dp_comm_destroy(tcnn_dp_comm* c) { delete c; }
 int tcnn_trainer_set_dp(tcnn_trainer* t, tcnn_dp_comm* c, int sharded) {
-	return guard([&] { t->t->set_dp(c ? c->c.get() : nullptr, sharded != 0); });
+	return guard([&] {
+		if (c) t->t->require_plain_adam("A data-parallel communicator");
+		t->t->set_dp(c ? c->c.get() : nullptr, sharded != 0);
+	});
 }
 uint64_t tcnn_dp_peer_blob_bytes(void) { return tcnn_amd::dp_peer_blob_bytes(); }
 int tcnn_trainer_dp_peer_export(tcnn_trainer* t, int nranks, int rank, void* blob) {
-	return guard([&] { t->t->dp_peer_export(nranks, rank, blob); });
+	return guard([&] {
+		t->t->require_plain_adam("The data-parallel peer exchange");
+		t->t->dp_peer_export(nranks, rank, blob);
+	});
 }
 int tcnn_trainer_dp_peer_attach(tcnn_trainer* t, const void* blobs) {
-	return guard([&] { t->t->dp_peer_attach(blobs); });
+	return guard([&] {
+		t->t->require_plain_adam("The data-parallel peer exchange");
+		t->t->dp_peer_attach(blobs);
+	});
 }
 int tcnn_trainer_dp_peer_detach(tcnn_trainer* t) {
 	return guard([&] { t->t->dp_peer_detach(); });
@@ -617,7 +636,10 @@ int tcnn_trainer_dp_peer_set_timeout(tcnn_trainer* t, double seconds) {
 	return guard([&] { t->t->dp_peer_set_timeout(seconds); });
 }
 int tcnn_debug_peer_loopback(tcnn_trainer* t, int nranks) {
-	return guard([&] { t->t->dp_peer_loopback(nranks); });
+	return guard([&] {
+		t->t->require_plain_adam("The data-parallel peer exchange");
+		t->t->dp_peer_loopback(nranks);
+	});
 }
 int tcnn_trainer_dp_peer_abandon(tcnn_trainer* t) {
 	return guard([&] { t->t->dp_peer_abandon(); });
@@ -663,6 +685,23 @@ uint64_t tcnn_trainer_n_params(const tcnn_trainer* t) { return t->t->n_params; }
 uint64_t tcnn_trainer_n_network_params(const tcnn_trainer* t) { return t->t->n_mlp; }
 float* tcnn_trainer_params_fp32(tcnn_trainer* t) { return t->t->w32.as<float>(); }
 void* tcnn_trainer_params(tcnn_trainer* t) { return t->t->w16.p; }
+void* tcnn_trainer_params_inference(tcnn_trainer* t) { return t->t->params_inference(); }
+int tcnn_trainer_optimizer_buffer(tcnn_trainer* t, const char* name, void** ptr, uint32_t* elem_bytes) {
+	return guard([&] {
+		TCNN_CHECK(name && ptr, "optimizer_buffer: null name or result pointer");
+		*ptr = t->t->optimizer_buffer(name, elem_bytes);
+	});
+}
+int tcnn_trainer_learning_rate(const tcnn_trainer* t, float* learning_rate) {
+	return guard([&] {
+		TCNN_CHECK(learning_rate != nullptr, "learning_rate: null result pointer");
+		*learning_rate = t->t->learning_rate();
+	});
+}
+const char* tcnn_trainer_optimizer_schedule(const tcnn_trainer* t) { return !t->t->opt ? "adam" : t->t->opt_inline ? "inline" : "staged"; }
+int tcnn_trainer_set_learning_rate(tcnn_trainer* t, float learning_rate) {
+	return guard([&] { t->t->set_learning_rate(learning_rate); });
+}
 void* tcnn_trainer_param_gradients(tcnn_trainer* t) { return t->t->g16.p; }
 float* tcnn_trainer_gradients_fp32(tcnn_trainer* t) { return t->t->g32.as<float>(); }
 int tcnn_trainer_optimizer_state(tcnn_trainer* t, float** m1, float** m2, uint32_t** steps) {
@@ -717,11 +756,11 @@ int tcnn_trainer_deserialize(tcnn_trainer* t, const void* buf, uint64_t size) {
 int tcnn_trainer_set_params_full_precision(tcnn_trainer* t, const float* host, uint64_t n) {
 	return guard([&] { t->t->set_params_full_precision(host, n); });
 }
-uint32_t tcnn_trainer_optimizer_step_count(const tcnn_trainer* t) { return t->t->adam_step; }
+uint32_t tcnn_trainer_optimizer_step_count(const tcnn_trainer* t) { return t->t->optimizer_step_count(); }
 int tcnn_trainer_update_hyperparams(tcnn_trainer* t, const char* params_json) {
 	return guard([&] {
 		const json p = json::parse(params_json);
-		if (p.count("optimizer")) t->t->adam.update(p["optimizer"]);  // Trainer::update_hyperparams, trainer.h:213-216
+		if (p.count("optimizer")) t->t->update_optimizer_hyperparams(p["optimizer"]);  // Trainer::update_hyperparams, trainer.h:213-216
 		// the reference forwards "loss" to Loss::update_hyperparams, which holds no hyperparameters
 		// (relative_l2.h, l2.h): the loss type is fixed at construction there too -- say so instead of
 		// ignoring a request to change it
@@ -736,7 +775,7 @@ const char* tcnn_trainer_hyperparams(tcnn_trainer* t) {
 	g_str.clear();
 	if (guard([&] {
 		    json h = json::object();
-		    h["optimizer"] = t->t->adam.hyperparams();
+		    h["optimizer"] = t->t->optimizer_hyperparams();
 		    h["loss"] = json::object();
 		    h["loss"]["otype"] = t->t->loss_otype;
 		    g_str = h.dump();

@@ -1,0 +1,323 @@
+// optimizer_tree.cpp -- the host side of the stacked optimizers (optimizer_tree.h): building the tree
+// from the "optimizer" block, its hyper-parameters, and the step schedule over the Trainer's buffers.
+// Semantics are the reference's (optimizers/sgd.h, exponential_decay.h, ema.h, lookahead.h, batched.h),
+// line references beside each piece.
+#include <cmath>
+
+#include "runtime.h"
+
+namespace tcnn_amd {
+
+namespace {
+bool has(const json& j, const char* k) { return j.is_object() && j.count(k); }
+}  // namespace
+
+std::string optimizer_otype_list() { return "Adam, SGD, ExponentialDecay, Ema, Lookahead, Batched"; }
+
+OptKind optimizer_kind_from_otype(const std::string& o) {  // optimizer.cu:49-80
+	if (ieq(o, "Adam")) return OptKind::Adam;
+	if (ieq(o, "SGD")) return OptKind::SGD;
+	if (ieq(o, "ExponentialDecay")) return OptKind::ExponentialDecay;
+	if (ieq(o, "Ema")) return OptKind::Ema;
+	if (ieq(o, "Lookahead")) return OptKind::Lookahead;
+	if (ieq(o, "Batched")) return OptKind::Batched;
+	if (ieq(o, "Shampoo"))
+		throw std::runtime_error("Cannot create `ShampooOptimizer` because tiny-cuda-nn was not compiled with cuBLAS and cuSolver. (supported: " +
+		                         optimizer_otype_list() + ")");
+	for (const char* refused : {"Average", "Novograd", "Composite"})
+		if (ieq(o, refused))
+			throw std::runtime_error("Optimizer '" + std::string(refused) + "' is not implemented by the MI355X engine (supported: " +
+			                         optimizer_otype_list() + ")");
+	throw std::runtime_error("Invalid optimizer type: " + o + " (supported: " + optimizer_otype_list() + ")");
+}
+
+std::unique_ptr<OptNode> TrainerHost::opt_build(const json& p) {
+	auto n = std::make_unique<OptNode>();
+	n->kind = optimizer_kind_from_otype(has(p, "otype") ? p["otype"].get<std::string>() : std::string("Adam"));
+	if (n->kind != OptKind::Adam && n->kind != OptKind::SGD) {
+		const json nested = has(p, "nested") ? p["nested"] : json::object();
+		TCNN_CHECK(nested.is_object(), "optimizer: 'nested' must be an object");
+		n->nested = opt_build(nested);
+	}
+	// the constructors' update_hyperparams(params): the nested block is applied a second time there,
+	// which changes nothing
+	opt_update(*n, p);
+	if (n->kind == OptKind::ExponentialDecay) {  // exponential_decay.h:52-53
+		n->lr_factor = 1.0f;
+		n->base_lr = opt_lr(*n->nested);
+	}
+	return n;
+}
+
+void TrainerHost::opt_update(OptNode& n, const json& p) {
+	auto u32 = [&](const char* k, uint32_t& v, bool positive) {
+		if (!has(p, k)) return;
+		const int64_t x = p[k].get<int64_t>();
+		TCNN_CHECK(x >= (positive ? 1 : 0) && x <= 0xffffffffll, std::string("optimizer: '") + k + "' is out of range");
+		v = (uint32_t)x;
+	};
+	switch (n.kind) {
+		case OptKind::Adam: adam.update(p); return;
+		case OptKind::SGD:  // sgd.h:116-124
+			if (has(p, "learning_rate")) n.sgd_lr = p["learning_rate"].get<float>();
+			if (has(p, "l2_reg")) n.sgd_l2_reg = p["l2_reg"].get<float>();
+			return;
+		case OptKind::ExponentialDecay:  // exponential_decay.h:103-123
+			if (has(p, "decay_base")) n.decay_base = p["decay_base"].get<float>();
+			u32("decay_interval", n.decay_interval, true);
+			u32("decay_start", n.decay_start, false);
+			u32("decay_end", n.decay_end, false);
+			break;
+		case OptKind::Ema:  // ema.h:167-179
+			if (has(p, "decay")) n.ema_decay = p["decay"].get<float>();
+			if (has(p, "full_precision")) {
+				const bool fp = p["full_precision"].get<bool>();
+				// tmp exists from allocation on (ema.h:96-99): the precision is fixed once the buffers are
+				TCNN_CHECK(fp == n.full_precision || !n.weights_ema.p, "optimizer: Ema 'full_precision' is fixed at construction");
+				n.full_precision = fp;
+			}
+			break;
+		case OptKind::Lookahead:  // lookahead.h:127-139
+			if (has(p, "alpha")) n.alpha = p["alpha"].get<float>();
+			u32("n_steps", n.n_steps, true);
+			break;
+		case OptKind::Batched:  // batched.h:120-128
+			u32("batch_size_multiplier", n.multiplier, true);
+			break;
+	}
+	if (has(p, "nested")) opt_update(*n.nested, p["nested"]);
+}
+
+json TrainerHost::opt_hyperparams(const OptNode& n) const {
+	json h = json::object();
+	switch (n.kind) {
+		case OptKind::Adam: return adam.hyperparams();
+		case OptKind::SGD:
+			h["otype"] = "SGD";
+			h["learning_rate"] = n.sgd_lr;
+			h["l2_reg"] = n.sgd_l2_reg;
+			return h;
+		case OptKind::ExponentialDecay:
+			h["otype"] = "ExponentialDecay";
+			h["decay_base"] = n.decay_base;
+			h["decay_interval"] = n.decay_interval;
+			h["decay_start"] = n.decay_start;
+			h["decay_end"] = n.decay_end;
+			break;
+		case OptKind::Ema:
+			h["otype"] = "EMA";
+			h["decay"] = n.ema_decay;
+			h["full_precision"] = n.full_precision;
+			break;
+		case OptKind::Lookahead:
+			h["otype"] = "Lookahead";
+			h["alpha"] = n.alpha;
+			h["n_steps"] = n.n_steps;
+			break;
+		case OptKind::Batched:
+			h["otype"] = "Batched";
+			h["batch_size_multiplier"] = n.multiplier;
+			break;
+	}
+	h["nested"] = opt_hyperparams(*n.nested);
+	return h;
+}
+
+uint32_t TrainerHost::opt_count(const OptNode& n) const {
+	switch (n.kind) {
+		case OptKind::Adam: return adam_step;
+		case OptKind::SGD: return n.sgd_step;
+		case OptKind::Batched: return n.batched_step;  // batched.h:99-101: its own counter
+		default: return opt_count(*n.nested);
+	}
+}
+
+float TrainerHost::opt_lr(const OptNode& n) const {
+	switch (n.kind) {
+		case OptKind::Adam: return adam.learning_rate;
+		case OptKind::SGD: return n.sgd_lr;
+		case OptKind::ExponentialDecay: return n.base_lr * n.lr_factor;  // exponential_decay.h:73-75
+		default: return opt_lr(*n.nested);
+	}
+}
+
+void TrainerHost::opt_set_lr(OptNode& n, float v) {
+	switch (n.kind) {
+		case OptKind::Adam: adam.learning_rate = v; return;
+		case OptKind::SGD: n.sgd_lr = v; return;
+		case OptKind::ExponentialDecay:  // exponential_decay.h:77-80
+			n.base_lr = v / n.lr_factor;
+			opt_set_lr(*n.nested, n.base_lr * n.lr_factor);
+			return;
+		default: opt_set_lr(*n.nested, v);
+	}
+}
+
+void* TrainerHost::opt_custom_weights(const OptNode& n) const {
+	switch (n.kind) {
+		case OptKind::Adam:
+		case OptKind::SGD: return nullptr;
+		case OptKind::Ema: return n.weights_ema.p;
+		case OptKind::Lookahead: return n.weights_lookahead.p;
+		default: return opt_custom_weights(*n.nested);
+	}
+}
+
+void TrainerHost::opt_allocate() {
+	for (OptNode* n = opt.get(); n; n = n->nested.get()) {
+		n->sgd_step = 0;
+		n->batched_step = 0;
+		n->lr_factor = 1.0f;
+		auto zeroed = [&](DevBuf& b, size_t bytes) {
+			b.reserve(bytes);
+			TCNN_HIP_CHECK(hipMemset(b.p, 0, bytes));
+		};
+		if (n->kind == OptKind::Ema) {
+			zeroed(n->weights_ema, n_params * 2);
+			if (n->full_precision) zeroed(n->tmp, n_params * 4);
+		} else if (n->kind == OptKind::Lookahead) {
+			zeroed(n->weights_lookahead, n_params * 2);
+		} else if (n->kind == OptKind::Batched) {
+			zeroed(n->pool, n_params * 4);
+			zeroed(n->pool16, n_params * 2);
+		}
+	}
+}
+
+void TrainerHost::opt_reset_weights() {
+	if (!opt) return;
+	if (void* cw = opt_custom_weights(*opt)) TCNN_HIP_CHECK(hipMemcpy(cw, w16.p, n_params * 2, hipMemcpyDeviceToDevice));
+}
+
+void* TrainerHost::params_inference() const {
+	void* cw = opt ? opt_custom_weights(*opt) : nullptr;
+	return cw ? cw : w16.p;
+}
+
+void* TrainerHost::optimizer_buffer(const std::string& name, uint32_t* elem_bytes) const {
+	for (const OptNode* n = opt.get(); n; n = n->nested.get()) {
+		const DevBuf* b = nullptr;
+		uint32_t eb = 2;
+		if (n->kind == OptKind::Ema && name == "weights_ema") b = &n->weights_ema;
+		if (n->kind == OptKind::Ema && name == "tmp" && n->full_precision) b = &n->tmp, eb = 4;
+		if (n->kind == OptKind::Lookahead && name == "weights_lookahead") b = &n->weights_lookahead;
+		if (n->kind == OptKind::Batched && name == "averaged_gradients") b = &n->pool, eb = 4;
+		if (n->kind == OptKind::Batched && name == "averaged_gradients_half") b = &n->pool16;
+		if (b) {
+			if (elem_bytes) *elem_bytes = eb;
+			return b->p;
+		}
+	}
+	return nullptr;
+}
+
+void TrainerHost::require_plain_adam(const char* what) const {
+	TCNN_CHECK(!opt, std::string(what) + " applies Adam itself and needs a plain Adam optimizer; this trainer's optimizer is '" +
+	                     opt_hyperparams(*opt)["otype"].get<std::string>() + "'");
+}
+
+void TrainerHost::update_optimizer_hyperparams(const json& p) {
+	if (opt) opt_update(*opt, p);
+	else adam.update(p);
+}
+
+json TrainerHost::optimizer_hyperparams() const { return opt ? opt_hyperparams(*opt) : adam.hyperparams(); }
+
+void TrainerHost::set_learning_rate(float v) {
+	if (opt) opt_set_lr(*opt, v);
+	else adam.learning_rate = v;
+}
+
+void TrainerHost::adam_apply(hipStream_t st, const float* grad32, float gscale, void* grad16) {  // AdamOptimizer::step, adam.h:150-188
+	++adam_step;
+	AdamArgs a = adam_args_table(st, adam_step);
+	a.grad_scale = gscale;
+	launch_adam(st, a, w32.as<float>(), w16.p, grad32, grad16, m1.as<float>(), m2.as<float>(), steps.as<uint32_t>());
+	ws.wimage_valid = false;
+}
+
+void TrainerHost::opt_step(OptNode& n, const OptStep& s) {
+	const size_t N = n_params;
+	switch (n.kind) {
+		case OptKind::Adam:
+			if (s.whole) {  // the engine's own step with Adam, as a plain-Adam trainer runs it
+				if (overlapped_ok()) training_step_overlapped(s.st, s.B, s.input, s.target, true);
+				else training_step_sequential(s.st, s.B, s.input, s.target, true);
+			} else {
+				adam_apply(s.st, s.g32, s.gscale, s.g16);
+			}
+			return;
+		case OptKind::SGD:  // sgd.h:82-94
+			TCNN_CHECK(!s.whole && s.g16, "optimizer: SGD steps on the fp16 gradients");
+			++n.sgd_step;
+			launch_sgd(s.st, w32.as<float>(), w16.p, s.g16, loss_scale, n.sgd_lr, n.sgd_l2_reg, N);
+			ws.wimage_valid = false;
+			return;
+		case OptKind::ExponentialDecay: {  // exponential_decay.h:60-71; step = the nested count before this step
+			const uint32_t step = opt_count(n);
+			if (step == 0) n.lr_factor = 1.0f;
+			if (step >= n.decay_start && (step - n.decay_start) % n.decay_interval == 0 && step <= n.decay_end) n.lr_factor *= n.decay_base;
+			opt_set_lr(*n.nested, n.base_lr * n.lr_factor);
+			opt_step(*n.nested, s);
+			return;
+		}
+		case OptKind::Ema: {  // ema.h:102-136: after the nested step, on the nested custom weights if any
+			opt_step(*n.nested, s);
+			const uint32_t step = opt_count(*n.nested);
+			// the reference's host expressions: std::pow(float, uint32_t) is pow(double, double)
+			const float debias_old = 1 - (float)std::pow((double)n.ema_decay, (double)(step - 1));
+			const float debias_new = 1.0f / (1 - (float)std::pow((double)n.ema_decay, (double)step));
+			const void* src = opt_custom_weights(*n.nested);
+			launch_ema(s.st, src ? src : w16.p, n.weights_ema.p, n.full_precision ? n.tmp.as<float>() : nullptr, n.ema_decay, debias_old,
+			           debias_new, N);
+			return;
+		}
+		case OptKind::Lookahead: {  // lookahead.h:78-96: before the nested step
+			const uint32_t step = opt_count(*n.nested);
+			// stream-ordered (the reference's cudaMemcpy blocks the host)
+			if (step == 0) TCNN_HIP_CHECK(hipMemcpyAsync(n.weights_lookahead.p, w16.p, N * 2, hipMemcpyDeviceToDevice, s.st));
+			if (step % n.n_steps == 0) {
+				launch_lookahead(s.st, w32.as<float>(), w16.p, n.weights_lookahead.p, n.alpha, N);
+				ws.wimage_valid = false;  // the training weights changed under the fused engine's weight image
+			}
+			opt_step(*n.nested, s);
+			return;
+		}
+		case OptKind::Batched: {  // batched.h:78-89
+			TCNN_CHECK(!s.whole && s.g16, "optimizer: Batched steps on the fp16 gradients");
+			launch_batched_pool(s.st, s.g16, n.pool.as<float>(), n.multiplier, n.batched_step % n.multiplier == 0, N);
+			++n.batched_step;
+			if (n.batched_step % n.multiplier == 0) {
+				launch_pool_cast(s.st, n.pool.as<float>(), n.pool16.p, N);
+				// the nested optimizer's gradients are the fp16 pool: an Adam below rounds pool x 1 to the same bits
+				OptStep inner = s;
+				inner.g32 = n.pool.as<float>();
+				inner.gscale = 1.0f;
+				inner.g16 = n.pool16.p;
+				opt_step(*n.nested, inner);
+			}
+			return;
+		}
+	}
+}
+
+// training_step(run_optimizer = true) of a trainer with a tree
+void TrainerHost::opt_training_step(hipStream_t st, uint32_t B, const float* input, const float* target) {
+	TCNN_CHECK(!dp && !peer_attached, "data-parallel training needs a plain Adam optimizer");
+	if (opt_inline) {
+		OptStep s;
+		s.st = st;
+		s.whole = true;
+		s.B = B;
+		s.input = input;
+		s.target = target;
+		opt_step(*opt, s);
+		return;
+	}
+	// something acts between the gradients and the inner update: the gradient pass, then the tree
+	if (overlapped_ok()) training_step_overlapped(st, B, input, target, false);
+	else training_step_sequential(st, B, input, target, false);
+	optimizer_step(st);
+}
+
+}  // namespace tcnn_amd

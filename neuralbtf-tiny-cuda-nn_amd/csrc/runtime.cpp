@@ -1211,8 +1211,14 @@ TrainerHost::TrainerHost(uint32_t n_in, uint32_t n_out, const json& cfg, uint32_
 	const int loss_type = loss_type_from_otype(loss_otype);
 	TCNN_CHECK(loss_type >= 0, "Loss '" + loss_otype + "' is not implemented by the MI355X engine (" + loss_otype_list() + ")");
 	const std::string oo = jval<std::string>(opt, "otype", "Adam");
-	TCNN_CHECK(ieq(oo, "Adam"), "Optimizer '" + oo + "' is not implemented by the MI355X engine yet");
-	adam.update(opt);
+	if (ieq(oo, "Adam")) {
+		adam.update(opt);
+	} else {  // a stacked optimizer or SGD (optimizer_tree.cpp); throws for the otypes the engine refuses
+		this->opt = opt_build(opt);
+		opt_inline = true;
+		for (const OptNode* n = this->opt.get(); n; n = n->nested.get())
+			if (n->kind != OptKind::Adam && n->kind != OptKind::ExponentialDecay && n->kind != OptKind::Ema) opt_inline = false;
+	}
 	model = std::make_unique<NetworkHost>(n_in, n_out, enc, net);
 	model->loss_type = (uint32_t)loss_type;
 	TCNN_CHECK(loss_type != LOSS_RELATIVE_L2_LUMINANCE || model->mlp.padded_output >= 6,
@@ -1255,6 +1261,11 @@ void TrainerHost::initialize_params_rng(Pcg32& rng) {
 	TCNN_HIP_CHECK(hipDeviceSynchronize());
 	adam_step = 0;
 	ws.wimage_valid = false;
+	if (this->opt) {
+		opt_allocate();
+		opt_reset_weights();
+		TCNN_HIP_CHECK(hipDeviceSynchronize());
+	}
 }
 
 void TrainerHost::set_params_full_precision(const float* host, uint64_t n) {
@@ -1264,6 +1275,7 @@ void TrainerHost::set_params_full_precision(const float* host, uint64_t n) {
 	launch_cast_f32_f16(nullptr, w32.as<float>(), w16.p, n_params);
 	ws.wimage_valid = false;
 	TCNN_HIP_CHECK(hipDeviceSynchronize());
+	opt_reset_weights();
 }
 
 void TrainerHost::training_step(hipStream_t st, uint32_t B, const float* input, const float* target, bool run_optimizer) {
@@ -1274,8 +1286,14 @@ void TrainerHost::training_step(hipStream_t st, uint32_t B, const float* input, 
 	}
 	// a whole step with the optimizer replays as a hipGraph when enabled (not on the steps that record
 	// phase events, not with AdaBound, whose bounds depend on the step)
-	if (run_optimizer && use_graph && !(timer.enabled && timer.sampling) && !adam.adabound && training_step_graph(st, B, input, target))
+	// (nor with a stacked optimizer, whose host-side schedule depends on the step: it steps eagerly)
+	if (run_optimizer && use_graph && !opt && !(timer.enabled && timer.sampling) && !adam.adabound &&
+	    training_step_graph(st, B, input, target))
 		return;
+	if (run_optimizer && opt) {
+		opt_training_step(st, B, input, target);
+		return;
+	}
 	if (run_optimizer) {
 		step_eager(st, B, input, target);
 		return;
@@ -1303,7 +1321,7 @@ void TrainerHost::training_step_sequential(hipStream_t st, uint32_t B, const flo
 	launch_sum(st, ws.loss_partial.as<float>(), ws.n_loss_partials, d_loss.as<float>());
 	mark(st, 4);
 	last_B = B;
-	if (run_optimizer) optimizer_step(st);
+	if (run_optimizer) adam_apply(st, g32.as<float>(), grad_scale, g16.p);
 }
 
 
@@ -1623,15 +1641,23 @@ AdamArgs TrainerHost::adam_args_table(hipStream_t st, uint32_t upto, uint32_t re
 	return a;
 }
 
-void TrainerHost::optimizer_step(hipStream_t st) {  // AdamOptimizer::step, adam.h:150-188
-	++adam_step;
-	const AdamArgs a = adam_args_table(st, adam_step);
-	launch_adam(st, a, w32.as<float>(), w16.p, g32.as<float>(), g16.p, m1.as<float>(), m2.as<float>(), steps.as<uint32_t>());
-	ws.wimage_valid = false;
+void TrainerHost::optimizer_step(hipStream_t st) {
+	if (opt) {  // the tree on the gradient buffers: the fp16 gradients first (Adam's own rounding of the sums)
+		launch_grad_f16(st, g32.as<float>(), g16.p, grad_scale, n_params);
+		OptStep s;
+		s.st = st;
+		s.g32 = g32.as<float>();
+		s.gscale = grad_scale;
+		s.g16 = g16.p;
+		opt_step(*opt, s);
+		return;
+	}
+	adam_apply(st, g32.as<float>(), grad_scale, g16.p);
 }
 
 std::unique_ptr<TrainerFwdCtx> TrainerHost::forward(hipStream_t st, uint32_t B, const float* input, const float* target, const float* pdf,
-                                                    const void* ext_dLdy16, bool prep_dinput, const float* perturbation) {
+                                                    const void* ext_dLdy16, bool prep_dinput, const float* perturbation,
+                                                    bool use_inference_params) {
 	TCNN_CHECK(B % BATCH_GRANULARITY == 0, "forward: batch size must be a multiple of 256");
 	TCNN_CHECK(ext_dLdy16 || target, "forward: a target (or an external dL/dy) is required");
 	NetworkHost& m = *model;
@@ -1639,7 +1665,10 @@ std::unique_ptr<TrainerFwdCtx> TrainerHost::forward(hipStream_t st, uint32_t B, 
 	auto c = std::make_unique<TrainerFwdCtx>();
 	c->B = B;
 	c->out16.reserve((size_t)B * OUTP * 2);
-	c->layout = m.forward_keep(st, ws, B, input, w16.p, c->out16.p, prep_dinput, c->keep);
+	// use_inference_params (trainer.h:97-112): the forward and its loss on the optimizer's custom weights
+	const void* params16 = use_inference_params ? params_inference() : w16.p;
+	c->inference_params = params16 != w16.p;
+	c->layout = m.forward_keep(st, ws, B, input, params16, c->out16.p, prep_dinput, c->keep);
 	if (ext_dLdy16) {  // trainer.h:126-130: the caller's dL/dy replaces the loss
 		c->ext = ext_dLdy16;
 	} else {
@@ -1661,6 +1690,9 @@ std::unique_ptr<TrainerFwdCtx> TrainerHost::forward(hipStream_t st, uint32_t B, 
 
 void TrainerHost::backward(hipStream_t st, const TrainerFwdCtx& c, uint32_t B, const float* input, float* dL_dinput, int gradient_mode) {
 	TCNN_CHECK(B == c.B, "backward: batch size differs from the forward's");
+	TCNN_CHECK(!c.inference_params,
+	           "backward: use_inference_params is honoured by inference and by a forward without a backward only; this context's "
+	           "forward read the optimizer's custom weights, and gradients are taken at the training parameters");
 	// Accumulate: this backward's gradients into a scratch sum, added afterwards (trainer.h:146-153).
 	// Ignore: the same scratch, never added -- the parameter gradients stay as they were and only
 	// dL/dinput is delivered (the engine's fused backward computes both in one pass).
@@ -1683,6 +1715,7 @@ float TrainerHost::ctx_loss(hipStream_t st, const TrainerFwdCtx& c) {  // traine
 }
 
 void TrainerHost::optimizer_step_range(hipStream_t st, uint64_t begin, uint64_t end) {
+	require_plain_adam("optimizer_step_range");
 	TCNN_CHECK(begin <= end && end <= n_params, "optimizer_step_range: range outside the parameter vector");
 	++adam_step;
 	AdamArgs a = adam_args_table(st, adam_step);
@@ -1702,7 +1735,9 @@ float TrainerHost::loss(hipStream_t st) {
 void TrainerHost::inference(hipStream_t st, uint32_t B, const float* input, float* out) {
 	const uint32_t OUTP = model->mlp.padded_output;
 	ws.out16.reserve((size_t)B * OUTP * 2);
-	model->inference(st, ws, B, input, w16.p, ws.out16.p, /*trust_image=*/true);
+	// the inference parameters (trainer.h:330-335); the weight image tracks the training parameters only
+	const void* p = params_inference();
+	model->inference(st, ws, B, input, p, ws.out16.p, /*trust_image=*/p == w16.p);
 	launch_trim_cast(st, B, OUTP, n_output_dims, ws.out16.p, out);
 }
 

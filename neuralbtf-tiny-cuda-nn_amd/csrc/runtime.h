@@ -15,6 +15,7 @@
 #include "common.h"
 #include "grid_device.h"
 #include "kernels.h"
+#include "optimizer_tree.h"
 
 namespace tcnn_amd {
 
@@ -242,6 +243,31 @@ struct AdamHost {
 	json hyperparams() const;
 };
 
+// One optimizer of a stacked "optimizer" block (optimizer_tree.h): its hyper-parameters, its host-side
+// state and its device buffers (allocated by TrainerHost::opt_allocate). An Adam node holds nothing:
+// Adam's hyper-parameters, step count and moments are the Trainer's (adam, adam_step, m1, m2, steps).
+struct OptNode {
+	OptKind kind = OptKind::Adam;
+	std::unique_ptr<OptNode> nested;
+	// SGD (sgd.h:146-152)
+	float sgd_lr = 1e-3f, sgd_l2_reg = 1e-8f;
+	uint32_t sgd_step = 0;
+	// ExponentialDecay (exponential_decay.h:153-159): the nested learning rate is base_lr * lr_factor
+	float decay_base = 0.1f, lr_factor = 1.0f, base_lr = 0.0f;
+	uint32_t decay_interval = 10000, decay_start = 10000, decay_end = 10000000;
+	// Ema (ema.h:209-214): weights_ema fp16 [n] (the inference parameters); tmp fp32 [n] with full_precision
+	float ema_decay = 0.99f;
+	bool full_precision = false;
+	DevBuf weights_ema, tmp;
+	// Lookahead (lookahead.h:163-167): weights_lookahead fp16 [n] (the inference parameters)
+	float alpha = 0.5f;
+	uint32_t n_steps = 16;
+	DevBuf weights_lookahead;
+	// Batched (batched.h:155-161): pool fp32 [n], its fp16 cast, own step counter
+	uint32_t multiplier = 16, batched_step = 0;
+	DevBuf pool, pool16;
+};
+
 // Encodings of the network input (reference encodings/*.h). An encoding is its list of parts, each
 // over its own input columns (composite.h, Concatenation): the multiresolution grid (parametric),
 // OneBlob (oneblob.h), Identity (identity.h), SphericalHarmonics and TriangleWave. An encoding that is
@@ -466,6 +492,7 @@ struct TrainerFwdCtx {
 	DevBuf out16, dLdy16, lpart;
 	DevBuf pert16;              // output + perturbation, what the loss saw (trainer.h:114-123)
 	const void* ext = nullptr;  // external dL/dy (not owned)
+	bool inference_params = false;  // the forward read the optimizer's custom weights: no backward
 	uint32_t n_lpart = 0;
 	const void* dLdy() const { return ext ? ext : dLdy16.p; }
 };
@@ -511,6 +538,51 @@ struct TrainerHost {
 	                              float* grad_out = nullptr, bool skip_reduce = false);
 	AdamArgs adam_args() const;
 
+	// ---- stacked optimizers (optimizer_tree.cpp). opt == nullptr: plain Adam, whose every path below
+	// is untouched. Otherwise opt owns the step: opt_inline (only ExponentialDecay / Ema above Adam)
+	// keeps Adam's schedule -- the learning rate is set on the host before it, one EMA launch follows --
+	// and every other tree runs the gradient pass of run_optimizer = false, then steps on the gradient
+	// buffers. ----
+	std::unique_ptr<OptNode> opt;
+	bool opt_inline = false;
+	// what one level's step reads: the fp32 gradient sums x gscale (Adam's input), their fp16 rounding
+	// (everybody else's); whole: the Adam leaf runs the engine's whole step with the optimizer on the batch
+	struct OptStep {
+		hipStream_t st = nullptr;
+		const float* g32 = nullptr;
+		float gscale = 1.0f;
+		void* g16 = nullptr;
+		bool whole = false;
+		uint32_t B = 0;
+		const float* input = nullptr;
+		const float* target = nullptr;
+	};
+	std::unique_ptr<OptNode> opt_build(const json& p);
+	void opt_allocate();      // (re)allocates and zeroes the tree's buffers and counters (initialize_params)
+	void opt_reset_weights();  // the custom-weights buffer <- the fp16 parameters (trainer.h:248-265)
+	void opt_update(OptNode& n, const json& p);
+	json opt_hyperparams(const OptNode& n) const;
+	uint32_t opt_count(const OptNode& n) const;  // Optimizer::step()
+	float opt_lr(const OptNode& n) const;
+	void opt_set_lr(OptNode& n, float v);
+	void* opt_custom_weights(const OptNode& n) const;
+	void opt_step(OptNode& n, const OptStep& s);
+	void opt_training_step(hipStream_t st, uint32_t B, const float* input, const float* target);
+	// Adam on the fp32 sums grad32 x gscale (fp16 gradients written to grad16)
+	void adam_apply(hipStream_t st, const float* grad32, float gscale, void* grad16);
+	void update_optimizer_hyperparams(const json& p);  // Trainer::update_hyperparams' "optimizer" block
+	json optimizer_hyperparams() const;
+	uint32_t optimizer_step_count() const { return opt ? opt_count(*opt) : adam_step; }
+	float learning_rate() const { return opt ? opt_lr(*opt) : adam.learning_rate; }
+	void set_learning_rate(float v);
+	// Trainer::params_inference(): the optimizer's custom weights, else the training parameters
+	void* params_inference() const;
+	// a named state buffer of the tree ("weights_ema", "tmp", "weights_lookahead", "averaged_gradients",
+	// "averaged_gradients_half"), outermost first; nullptr when the tree has none
+	void* optimizer_buffer(const std::string& name, uint32_t* elem_bytes) const;
+	// the data-parallel schedules and optimizer_step_range apply Adam themselves
+	void require_plain_adam(const char* what) const;
+
 	TrainerHost(uint32_t n_in, uint32_t n_out, const json& cfg, uint32_t seed);
 	void initialize_params(uint32_t seed);
 	void initialize_params_rng(Pcg32& rng);  // from the caller's generator (advanced by n_params draws)
@@ -526,7 +598,8 @@ struct TrainerHost {
 	// optimizer_step() reads.
 	// perturbation (nullable): fp32 [B][padded output] noise added to the output before the loss
 	std::unique_ptr<TrainerFwdCtx> forward(hipStream_t st, uint32_t B, const float* input, const float* target, const float* pdf,
-	                                       const void* ext_dLdy16, bool prep_dinput, const float* perturbation = nullptr);
+	                                       const void* ext_dLdy16, bool prep_dinput, const float* perturbation = nullptr,
+	                                       bool use_inference_params = false);
 	// gradient_mode: 0 Overwrite, 1 Accumulate, 2 Ignore (GradientMode, common.h)
 	void backward(hipStream_t st, const TrainerFwdCtx& c, uint32_t B, const float* input, float* dL_dinput, int gradient_mode);
 	float ctx_loss(hipStream_t st, const TrainerFwdCtx& c);

@@ -271,22 +271,66 @@ std::vector<uint8_t> TrainerHost::serialize(bool with_optimizer) {
 	w.map(with_optimizer ? 4 : 3);
 	w.str("n_params");
 	w.uint(n);
-	if (with_optimizer) {  // AdamOptimizer::serialize (adam.h:278-286)
+	// Optimizer::serialize of one level, keys in lexicographic order; node == nullptr: the Trainer's Adam
+	std::function<void(const OptNode*)> write_opt = [&](const OptNode* node) {
+		auto bin = [&](const char* key, const DevBuf& b, size_t bytes) {
+			const auto h = d2h(b, bytes);
+			w.str(key);
+			w.bin(h.data(), h.size());
+		};
+		if (!node || node->kind == OptKind::Adam) {  // AdamOptimizer::serialize (adam.h:278-286)
+			w.map(5);
+			w.str("base_learning_rate");
+			w.flt(adam.learning_rate);
+			w.str("current_step");
+			w.uint(adam_step);
+			const auto m1h = d2h(m1, n * 4), m2h = d2h(m2, n * 4), sth = d2h(steps, n * 4);
+			w.str("first_moments_binary");
+			w.bin(m1h.data(), m1h.size());
+			w.str("param_steps_binary");
+			w.bin(sth.data(), sth.size());
+			w.str("second_moments_binary");
+			w.bin(m2h.data(), m2h.size());
+			return;
+		}
+		switch (node->kind) {
+			case OptKind::SGD:  // sgd.h:134-139
+				w.map(2);
+				w.str("current_step");
+				w.uint(node->sgd_step);
+				w.str("learning_rate");
+				w.flt(node->sgd_lr);
+				return;
+			case OptKind::ExponentialDecay:  // exponential_decay.h:136-142
+				w.map(3);
+				w.str("learning_rate");
+				w.flt(node->base_lr);
+				w.str("learning_rate_factor");
+				w.flt(node->lr_factor);
+				break;
+			case OptKind::Batched:  // batched.h:138-145
+				w.map(4);
+				bin("averaged_gradients_binary", node->pool, n * 4);
+				bin("averaged_gradients_half_binary", node->pool16, n * 2);
+				w.str("current_step");
+				w.uint(node->batched_step);
+				break;
+			default:  // Ema (ema.h:190-195), Lookahead (lookahead.h:150-155): "nested" sorts first
+				w.map(2);
+				break;
+		}
+		w.str("nested");
+		write_opt(node->nested.get());
+		if (node->kind == OptKind::Ema) bin("weights_ema_binary", node->weights_ema, n * 2);
+		if (node->kind == OptKind::Lookahead) bin("weights_lookahead_binary", node->weights_lookahead, n * 2);
+	};
+	if (with_optimizer) {
 		w.str("optimizer");
-		w.map(5);
-		w.str("base_learning_rate");
-		w.flt(adam.learning_rate);
-		w.str("current_step");
-		w.uint(adam_step);
-		const auto m1h = d2h(m1, n * 4), m2h = d2h(m2, n * 4), sth = d2h(steps, n * 4);
-		w.str("first_moments_binary");
-		w.bin(m1h.data(), m1h.size());
-		w.str("param_steps_binary");
-		w.bin(sth.data(), sth.size());
-		w.str("second_moments_binary");
-		w.bin(m2h.data(), m2h.size());
+		write_opt(opt.get());
 	}
-	const auto ph = d2h(w16, n * 2);
+	// the inference parameters (trainer.h:281)
+	std::vector<uint8_t> ph(n * 2);
+	if (n) TCNN_HIP_CHECK(hipMemcpy(ph.data(), params_inference(), n * 2, hipMemcpyDeviceToHost));
 	w.str("params_binary");
 	w.bin(ph.data(), ph.size());
 	w.str("params_type");
@@ -319,11 +363,45 @@ void TrainerHost::deserialize(const void* data, size_t size) {
 		launch_cast_f16_f32(nullptr, w16.p, w32.as<float>(), n);
 		TCNN_HIP_CHECK(hipDeviceSynchronize());
 		ws.wimage_valid = false;
+		opt_reset_weights();  // set_params (trainer.h:256-269): both parameter sets
 	} else {
 		throw std::runtime_error("Trainer: snapshot parameters must be of type float of __half");
 	}
-	if (root.has("optimizer")) {  // AdamOptimizer::deserialize (adam.h:288-299)
-		const MsgValue& o = root.at("optimizer");
+	// Optimizer::deserialize of the wrappers, down to the innermost level
+	const MsgValue* lvl = root.has("optimizer") ? &root.at("optimizer") : nullptr;
+	bool adam_level = lvl != nullptr;
+	for (OptNode* node = lvl ? opt.get() : nullptr; node; node = node->nested.get()) {
+		auto upload = [&](DevBuf& b, const char* key, size_t bytes) {
+			TCNN_HIP_CHECK(hipMemcpy(b.p, bin_of(lvl->at(key), bytes, key).data(), bytes, hipMemcpyHostToDevice));
+		};
+		switch (node->kind) {
+			case OptKind::Adam: break;
+			case OptKind::SGD:  // sgd.h:141-144
+				node->sgd_step = (uint32_t)lvl->at("current_step").number();
+				node->sgd_lr = (float)lvl->at("learning_rate").number();
+				adam_level = false;
+				break;
+			case OptKind::ExponentialDecay:  // exponential_decay.h:144-148
+				node->base_lr = (float)lvl->at("learning_rate").number();
+				node->lr_factor = lvl->has("learning_rate_factor") ? (float)lvl->at("learning_rate_factor").number() : 1.0f;
+				break;
+			case OptKind::Ema:  // ema.h:197-206: with full precision, tmp restarts from the fp16 average
+				upload(node->weights_ema, "weights_ema_binary", n * 2);
+				if (node->full_precision) launch_cast_f16_f32(nullptr, node->weights_ema.p, node->tmp.as<float>(), n);
+				break;
+			case OptKind::Lookahead:  // lookahead.h:157-160
+				upload(node->weights_lookahead, "weights_lookahead_binary", n * 2);
+				break;
+			case OptKind::Batched:  // batched.h:147-152
+				node->batched_step = (uint32_t)lvl->at("current_step").number();
+				upload(node->pool, "averaged_gradients_binary", n * 4);
+				upload(node->pool16, "averaged_gradients_half_binary", n * 2);
+				break;
+		}
+		if (node->nested) lvl = &lvl->at("nested");
+	}
+	if (adam_level) {  // AdamOptimizer::deserialize (adam.h:288-299)
+		const MsgValue& o = *lvl;
 		TCNN_HIP_CHECK(hipMemcpy(m1.p, bin_of(o.at("first_moments_binary"), n * 4, "first_moments_binary").data(), n * 4,
 		                         hipMemcpyHostToDevice));
 		TCNN_HIP_CHECK(hipMemcpy(m2.p, bin_of(o.at("second_moments_binary"), n * 4, "second_moments_binary").data(), n * 4,

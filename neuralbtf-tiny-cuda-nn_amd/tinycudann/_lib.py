@@ -60,6 +60,7 @@ _SIGS = {
     "tcnn_trainer_optimizer_step": (c_int, [c_void_p, c_void_p]),
     "tcnn_trainer_forward": (c_void_p, [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
     "tcnn_trainer_forward_perturbed": (c_void_p, [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
+    "tcnn_trainer_forward_inference_params": (c_void_p, [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "tcnn_trainer_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_int]),
     "tcnn_trainer_context_loss": (c_float, [c_void_p, c_void_p, c_void_p]),
     "tcnn_trainer_context_loss_value": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -83,6 +84,11 @@ _SIGS = {
     "tcnn_trainer_n_network_params": (c_uint64, [c_void_p]),
     "tcnn_trainer_params_fp32": (c_void_p, [c_void_p]),
     "tcnn_trainer_params": (c_void_p, [c_void_p]),
+    "tcnn_trainer_params_inference": (c_void_p, [c_void_p]),
+    "tcnn_trainer_optimizer_buffer": (c_int, [c_void_p, c_char_p, c_void_p, c_void_p]),
+    "tcnn_trainer_learning_rate": (c_int, [c_void_p, c_void_p]),
+    "tcnn_trainer_optimizer_schedule": (c_char_p, [c_void_p]),
+    "tcnn_trainer_set_learning_rate": (c_int, [c_void_p, c_float]),
     "tcnn_trainer_param_gradients": (c_void_p, [c_void_p]),
     "tcnn_trainer_gradients_fp32": (c_void_p, [c_void_p]),
     "tcnn_trainer_set_gradient_scale": (c_int, [c_void_p, c_float]),

@@ -36,6 +36,11 @@ class Trainer:
     def inference_engine(self):
         return L.lib().tcnn_trainer_inference_engine(self.h).decode()
 
+    @property
+    def optimizer_schedule(self):
+        """"adam", "inline" or "staged" (tcnn_trainer_optimizer_schedule)"""
+        return L.lib().tcnn_trainer_optimizer_schedule(self.h).decode()
+
     def training_step(self, input, target, run_optimizer=True, stream=None):
         """input: float32 [B, n_in] CUDA, target float32 [B, n_out] CUDA (contiguous)."""
         assert input.is_contiguous() and target.is_contiguous()
@@ -56,13 +61,20 @@ class Trainer:
     def padded_output_width(self):
         return L.lib().tcnn_trainer_padded_output_width(self.h)
 
-    def forward(self, input, target=None, data_pdf=None, external_dL_dy=None, prepare_input_gradients=False, stream=None):
+    def forward(self, input, target=None, data_pdf=None, external_dL_dy=None, prepare_input_gradients=False, stream=None,
+                use_inference_params=False):
         """Trainer::forward (trainer.h:97-144): network output + loss on target (optionally weighted by
         data_pdf float32 [B, n_out]), or the caller's loss-scaled dL/dy (float16 [B, padded_output_width]).
-        Returns a ForwardContext for backward() / its loss()."""
+        Returns a ForwardContext for backward() / its loss(). use_inference_params: output and loss at
+        params_inference(); backward() refuses such a context."""
         for t in (input, target, data_pdf, external_dL_dy):
             assert t is None or t.is_contiguous()
         ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else 0)
+        if use_inference_params:
+            assert not prepare_input_gradients
+            h = L.lib().tcnn_trainer_forward_inference_params(self.h, _stream(stream), input.shape[0], ptr(input), ptr(target),
+                                                              ptr(data_pdf), ptr(external_dL_dy))
+            return ForwardContext(self, L.check_ptr(h), input.shape[0], (input, target, data_pdf, external_dL_dy))
         h = L.lib().tcnn_trainer_forward(self.h, _stream(stream), input.shape[0], ptr(input), ptr(target), ptr(data_pdf),
                                          ptr(external_dL_dy), int(prepare_input_gradients))
         return ForwardContext(self, L.check_ptr(h), input.shape[0], (input, target, data_pdf, external_dL_dy))
@@ -166,6 +178,12 @@ class Trainer:
         import torch
         return self._view(L.lib().tcnn_trainer_params(self.h), self.n_params, torch.float16)
 
+    def params_inference(self):
+        """Trainer::params_inference() (trainer.h:234-236): the fp16 parameters inference() and serialize() read --
+        the optimizer's custom weights (Ema, Lookahead), else params()."""
+        import torch
+        return self._view(L.lib().tcnn_trainer_params_inference(self.h), self.n_params, torch.float16)
+
     def param_gradients(self):
         import torch
         return self._view(L.lib().tcnn_trainer_param_gradients(self.h), self.n_params, torch.float16)
@@ -174,9 +192,44 @@ class Trainer:
         import torch
         return self._view(L.lib().tcnn_trainer_gradients_fp32(self.h), self.n_params, torch.float32)
 
-    def optimizer_state(self):
-        """(first moments fp32, second moments fp32, per-parameter step counts int32) views (adam.h:128-148)"""
+    _OPTIMIZER_BUFFERS = ("weights_ema", "tmp", "weights_lookahead", "averaged_gradients", "averaged_gradients_half")
+
+    def optimizer_buffers(self):
+        """{name: view} of a stacked optimizer's state buffers (Ema weights_ema / tmp, Lookahead
+        weights_lookahead, Batched averaged_gradients / averaged_gradients_half); {} for plain Adam."""
         import torch
+        out = {}
+        for name in self._OPTIMIZER_BUFFERS:
+            p, eb = ctypes.c_void_p(), ctypes.c_uint32(0)
+            L.check(L.lib().tcnn_trainer_optimizer_buffer(self.h, name.encode(), ctypes.byref(p), ctypes.byref(eb)))
+            if p.value:
+                out[name] = self._view(p.value, self.n_params, torch.float32 if eb.value == 4 else torch.float16)
+        return out
+
+    def learning_rate(self):
+        """Optimizer::learning_rate() of the outermost optimizer."""
+        v = ctypes.c_float(0.0)
+        L.check(L.lib().tcnn_trainer_learning_rate(self.h, ctypes.byref(v)))
+        return v.value
+
+    def set_learning_rate(self, v):
+        L.check(L.lib().tcnn_trainer_set_learning_rate(self.h, float(v)))
+
+    def update_hyperparams(self, params):
+        """Trainer::update_hyperparams (trainer.h:213-216): {"optimizer": {..., "nested": {...}}}."""
+        L.check(L.lib().tcnn_trainer_update_hyperparams(self.h, json.dumps(params).encode()))
+
+    def hyperparams(self):
+        """{"optimizer": the optimizer tree's hyperparams, "loss": {"otype"}}"""
+        return json.loads(L.check_ptr(L.lib().tcnn_trainer_hyperparams(self.h)).decode())
+
+    def optimizer_state(self, stacked=False):
+        """(first moments fp32, second moments fp32, per-parameter step counts int32) views (adam.h:128-148);
+        stacked=True: a dict of those ("first_moments", "second_moments", "param_steps") and optimizer_buffers()."""
+        import torch
+        if stacked:
+            m1, m2, st = self.optimizer_state()
+            return dict(self.optimizer_buffers(), first_moments=m1, second_moments=m2, param_steps=st)
         m1, m2, st = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
         L.check(L.lib().tcnn_trainer_optimizer_state(self.h, ctypes.byref(m1), ctypes.byref(m2), ctypes.byref(st)))
         return (self._view(m1.value, self.n_params, torch.float32), self._view(m2.value, self.n_params, torch.float32),
