@@ -331,6 +331,10 @@ const char* tcnn_trainer_inference_engine(const tcnn_trainer* t);
 /* The same for a network module (NetworkWithInputEncoding / create_network); "encoding" for encodings. */
 const char* tcnn_module_engine(const tcnn_module* m);
 const char* tcnn_module_inference_engine(const tcnn_module* m);
+/* The kernel family tcnn_module_backward runs for this module, with or without dL/dinput requested:
+ * "register" (grid + W <= 64 in one register-resident kernel; never with dL/dinput), "tile", "layered";
+ * "encoding" for encodings. */
+const char* tcnn_module_backward_kernel(const tcnn_module* m, int with_dinput);
 /* set_max_level on the trainer model's grid encoding (see tcnn_module_set_max_level) */
 int tcnn_trainer_set_max_level(tcnn_trainer* t, float max_level);
 

@@ -110,6 +110,7 @@ struct ModuleBase {
 	size_t elem_bytes() const { return precision() == TCNN_PRECISION_FP32 ? 4 : 2; }
 	virtual const char* engine() const { return "encoding"; }
 	virtual const char* inference_engine() const { return "encoding"; }
+	virtual const char* backward_kernel(bool) const { return "encoding"; }
 	virtual uint32_t n_input_dims() const = 0;
 	virtual uint32_t n_output_dims() const = 0;
 	virtual uint64_t n_params() const = 0;
@@ -173,7 +174,7 @@ struct ModuleNWIE : ModuleBase {
 		const NwieCtx* c = dynamic_cast<const NwieCtx*>(ctx);
 		const bool use = c && c->keep && c->layout != NetworkHost::KEEP_NONE && c->in == in && c->params == params;
 		const void* dout = dL_dout;
-		const bool fused = model.fused_ok() && !dL_din;
+		const bool fused = model.backward_kernel_kind(dL_din != nullptr) == NetworkHost::BackwardKernel::Register;
 		model.grad_fin_done = false;
 		if (fused) {
 			model.ext_dout_scale = s;
@@ -202,6 +203,7 @@ struct ModuleNWIE : ModuleBase {
 	GridEncodingHost* grid_encoding() override { return model.grid; }
 	const char* engine() const override { return model.engine(); }
 	const char* inference_engine() const override { return model.inference_engine(); }
+	const char* backward_kernel(bool with_dinput) const override { return model.backward_kernel(with_dinput); }
 	uint32_t n_input_dims() const override { return model.n_input_dims; }
 	uint32_t n_output_dims() const override { return model.mlp.padded_output; }
 	uint64_t n_params() const override { return model.n_params(); }
@@ -800,6 +802,7 @@ const char* tcnn_trainer_engine(const tcnn_trainer* t) { return t->t->model->eng
 const char* tcnn_trainer_inference_engine(const tcnn_trainer* t) { return t->t->model->inference_engine(); }
 const char* tcnn_module_engine(const tcnn_module* m) { return m->m->engine(); }
 const char* tcnn_module_inference_engine(const tcnn_module* m) { return m->m->inference_engine(); }
+const char* tcnn_module_backward_kernel(const tcnn_module* m, int with_dinput) { return m->m->backward_kernel(with_dinput != 0); }
 int tcnn_trainer_set_max_level(tcnn_trainer* t, float max_level) {
 	return guard([&] {
 		TCNN_CHECK(t->t->model->grid != nullptr, "trainer model has no grid encoding");

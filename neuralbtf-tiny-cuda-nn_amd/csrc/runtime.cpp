@@ -972,13 +972,29 @@ int NetworkHost::forward_keep(hipStream_t st, StepWorkspace& ws, uint32_t B, con
 	return KEEP_NONE;
 }
 
+NetworkHost::BackwardKernel NetworkHost::backward_kernel_kind(bool with_dinput) const {
+	if (fused_ok() && !with_dinput) return BackwardKernel::Register;
+	if (tile_shape_ok()) return BackwardKernel::Tile;
+	return layered_ok() ? BackwardKernel::Layered : BackwardKernel::Unsupported;
+}
+
+const char* NetworkHost::backward_kernel(bool with_dinput) const {
+	switch (backward_kernel_kind(with_dinput)) {
+		case BackwardKernel::Register: return "register";
+		case BackwardKernel::Tile: return "tile";
+		case BackwardKernel::Layered: return "layered";
+		default: return "unsupported";
+	}
+}
+
 void NetworkHost::fwd_bwd(hipStream_t st, StepWorkspace& ws, uint32_t B, const float* pos, const float* target, uint32_t dims,
                           float loss_scale, const void* params16, const void* dout16, void* out16, float* grad32,
                           const std::function<void(int)>& mark, float* dL_dinput, const void* kept, int kept_layout) {
-	if (fused_ok() && !dL_dinput)
+	const BackwardKernel k = backward_kernel_kind(dL_dinput != nullptr);
+	if (k == BackwardKernel::Register)
 		fwd_bwd_fused(st, ws, B, pos, target, dims, loss_scale, params16, dout16, out16, grad32, mark,
 		              kept_layout == KEEP_FUSED_SOA ? kept : nullptr);
-	else if (tile_shape_ok())
+	else if (k == BackwardKernel::Tile)
 		fwd_bwd_tile(st, ws, B, pos, target, dims, loss_scale, params16, dout16, out16, grad32, mark, dL_dinput,
 		             kept_layout == KEEP_TILE_AOS ? kept : nullptr);
 	else fwd_bwd_layered(st, ws, B, pos, target, dims, loss_scale, params16, dout16, out16, grad32, mark, dL_dinput);

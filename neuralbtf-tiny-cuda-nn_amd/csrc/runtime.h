@@ -396,6 +396,12 @@ struct NetworkHost {
 	bool layered_ok() const;
 	const char* engine() const { return (fused_ok() || tile_ok()) ? "fused" : layered_ok() ? "layered" : "unsupported"; }
 	const char* inference_engine() const;  // "fused" (one MLP launch) or "layered"
+	// the kernel family fwd_bwd dispatches to (with_dinput: the caller wants dL/dinput): the register-resident
+	// kernel (mlp_fused.h), the tile kernel (mlp_tile.h) or one kernel per layer; backward_kernel names it
+	// "register" / "tile" / "layered" / "unsupported"
+	enum class BackwardKernel { Register, Tile, Layered, Unsupported };
+	BackwardKernel backward_kernel_kind(bool with_dinput) const;
+	const char* backward_kernel(bool with_dinput) const;
 	void initialize_params(Pcg32& rng, float* host_out, float scale = 1.0f) const;  // network first (nwie.h:124-130)
 
 	// params16: [mlp | encoding] fp16. out16: fp16 [B][padded_output].

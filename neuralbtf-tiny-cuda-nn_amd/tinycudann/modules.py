@@ -152,6 +152,11 @@ class _NativeModule:
     def inference_engine(self):
         return L.lib().tcnn_module_inference_engine(self.h).decode()
 
+    def backward_kernel(self, with_dinput):
+        """the kernel family a backward runs, with or without dL/dinput: "register", "tile", "layered"
+        ("encoding" for encodings)"""
+        return L.lib().tcnn_module_backward_kernel(self.h, int(bool(with_dinput))).decode()
+
     def initial_params(self, seed):
         p = torch.zeros(self.n_params(), dtype=torch.float32, device="cuda")
         torch.cuda.synchronize()

@@ -168,15 +168,27 @@ def assert_wgrad_per_element(got, ref, mag, ulps=8, fp16_out=False, floor_rel=1e
     return float(r[k])
 
 
-def relu_margin_ok(W, IN, NH, params16, x_rows, tau=2.0 ** -11, check_output=False):
+def relu_margin_ok(W, IN, NH, params16, x_rows, tau=2.0 ** -11, check_output=False, scale=1.0, act="ReLU", out_rows=0):
     """Per sample: True when no hidden pre-activation of the ReLU MLP lies within tau * sum_k |w_k a_k|
     of zero. At such a boundary fp32-MFMA and CPU summation orders may legitimately take different
     ReLU branches (a discrete difference no rounding bound covers); per-element gradient checks run on
     batches of samples clear of it, the aggregate checks on every sample. tau = 2^-11 covers one fp16
     ulp of difference in any single input term (|w_k| ulp(a_k) <= 2^-11 |w_k a_k|) plus the fp32
     summation-order noise. check_output (loss-driven steps): also False when the output's fp16 rounding
-    is within 2^-18 sum |w a| of a rounding boundary. x_rows: float [B][IN] (the fp16 encoded input values)."""
+    is within 2^-18 sum |w a| of a rounding boundary. x_rows: float [B][IN] (the fp16 encoded input values).
+    scale: the parameters are fp16(scale * params16) (a test's per-case constant). act: the hidden
+    activation; only ReLU and LeakyReLU (act = "LeakyReLU": the same boundary, the leaky forward) have a
+    branch, any other name checks no hidden layer. out_rows > 0: the network's output activation is
+    branchy too -- also False when one of the out_rows output pre-activations is within the margin of
+    zero. NH = 0 has no hidden layer: only out_rows can exclude a sample."""
     p = O.h2f(np.asarray(params16, np.uint16)).astype(np.float64)
+    if scale != 1.0:
+        p = O.h2f(O.f2h((p * scale).astype(np.float32))).astype(np.float64)
+    leaky = act.lower() == "leakyrelu"
+    branchy = act.lower() in ("relu", "leakyrelu")
+    assert branchy or not check_output, "check_output needs a ReLU or LeakyReLU network: " + act
+    assert branchy or act.lower() == "none" or out_rows == 0 or NH == 0, \
+        "the hidden activation must be None, ReLU or LeakyReLU when out_rows > 0: " + act
     mats, off, k = [], 0, IN
     for _ in range(NH):
         mats.append(p[off:off + W * k].reshape(W, k))
@@ -184,11 +196,18 @@ def relu_margin_ok(W, IN, NH, params16, x_rows, tau=2.0 ** -11, check_output=Fal
         k = W
     a = np.asarray(x_rows, np.float64)
     ok = np.ones(a.shape[0], bool)
+    if not branchy:
+        for Wm in mats:  # hidden None: linear layers, no branch (any other name: only reached with out_rows == 0)
+            a = (a @ Wm.T).astype(np.float16).astype(np.float64)
+        mats = []
     for Wm in mats:
         z = a @ Wm.T
         mag = np.abs(a) @ np.abs(Wm).T
         ok &= np.all(np.abs(z) >= tau * mag, axis=1)
-        a = np.maximum(z, 0.0).astype(np.float16).astype(np.float64)  # the fp16 post-activation
+        a = np.where(z > 0.0, z, 0.01 * z if leaky else 0.0).astype(np.float16).astype(np.float64)  # the fp16 post-activation
+    if out_rows:
+        Wo = p[off:off + out_rows * k].reshape(out_rows, k)
+        ok &= np.all(np.abs(a @ Wo.T) >= tau * (np.abs(a) @ np.abs(Wo).T), axis=1)
     if not check_output:
         return ok
     # the output's fp16 rounding: both sides must round to the same value, else the loss gradient

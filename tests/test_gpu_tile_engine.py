@@ -21,6 +21,8 @@ import json
 import numpy as np
 import pytest
 
+import mlp_reference as R
+import module_matrix_cases as C
 from helpers import CONFIG_HASH, CONFIG_ONEBLOB, assert_within_fp16_ulps, make_batch, rel_err, trainer_arrays
 from oracle import oracle as O
 
@@ -172,12 +174,12 @@ def test_module_forward_context_reused_by_backward(torch_mod, name):
     L.check(lib.tcnn_module_initialize_params(m, 42, ctypes.c_void_p(p32.data_ptr()), 1.0))
     p16 = p32.half().contiguous()
     B = 1024
-    xs = [torch.from_numpy(make_batch(B, seed=s)[0]).cuda() for s in (11, 12)]
+    params16 = p16.cpu().numpy().view(np.uint16)
+    # the first batch: ReLU-clear positions (its gradient is checked per element below), the second any
+    x0, enc_rows, dout_bits = C.context_reuse_inputs(cfg, params16, B)
+    xs = [torch.from_numpy(x0).cuda(), torch.from_numpy(make_batch(B, seed=12)[0]).cuda()]
     outs = [torch.empty(B, 16, dtype=torch.float16, device="cuda") for _ in xs]
-    rng = np.random.default_rng(0)
-    dout = np.zeros((B, 16), np.float32)
-    dout[:, :3] = rng.standard_normal((B, 3)) * 0.05
-    dout16 = torch.from_numpy(dout).half().cuda()
+    dout16 = torch.from_numpy(dout_bits.view(np.float16)).cuda()
     P = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
     ctxs = [L.check_ptr(lib.tcnn_module_forward(m, None, B, P(x), P(o), P(p16), 0)) for x, o in zip(xs, outs)]
 
@@ -195,9 +197,22 @@ def test_module_forward_context_reused_by_backward(torch_mod, name):
     # oracle: the network output and the gradient of the first batch
     om = O.OracleModel(cfg, 2, 3, seed=1337)
     inf = lambda x: om.inference(x, n_threads=4)  # noqa: E731
-    params16 = p16.cpu().numpy().view(np.uint16)
     om.w16[:] = params16
     assert_within_fp16_ulps(O.h2f(outs[0].cpu().numpy().view(np.uint16))[:, :3], O.h2f(inf(xs[0].cpu().numpy()))[:, :3])
+    # ... and the gradient: the network part against the float64 reference (tests/mlp_reference.py) of the
+    # encoded rows, per element and per matrix (the bound carries the fp16 rounding of the returned gradient
+    # per element: the 1e-4 grid initialisation puts these gradients in the fp16 subnormals, where a relative
+    # L2 bar would mostly measure that rounding); the grid part against the oracle's grid backward of the
+    # reference's dL/d(encoding), 1e-3 as in test_gpu_grid_input.py. CPU proof: test_mlp_reference.py.
+    net = cfg["network"]
+    W, NH = net["n_neurons"], net["n_hidden_layers"]
+    IN, nm, g = C.encoded_dims(cfg)
+    ref = R.mlp_reference(W, IN, NH, 16, net["activation"], net["output_activation"], params16[:nm], enc_rows, dout_bits)
+    R.check_output(O.h2f(outs[0].cpu().numpy().view(np.uint16))[:, :3], ref["out"][:, :3])
+    R.check_wgrad(g_first[:nm], ref, fp16_out=True)
+    if g is not None:
+        denc_soa = np.ascontiguousarray(O.f2h(ref["dinput"].astype(np.float32)).T)
+        assert rel_err(g_first[nm:], O.grid_bwd(g, x0, denc_soa)) <= 1e-3
     for c in ctxs + [ctx_other]:
         lib.tcnn_context_destroy(c)
     lib.tcnn_module_destroy(m)
