@@ -9,6 +9,7 @@
 #include <torch/extension.h>
 
 #include <c10/hip/HIPStream.h>
+#include <torch/csrc/jit/python/python_ivalue.h>
 
 #include "../../include/tcnn_mi355x.h"
 
@@ -36,16 +37,20 @@ tcnn_context* native(const torch::autograd::AutogradContext* ctx) {
 	return v.isNone() ? nullptr : v.toCustomClass<NativeCtx>()->c;
 }
 
+// The handle is a plain integer; saved_data["owner"] holds a reference to the Python object that destroys the
+// engine module when it is collected (tinycudann.modules._NativeModule), so the module lives as long as any
+// graph node that will call into it -- as the Python node's ctx.native_tcnn_module does.
 tcnn_module* module_of(const torch::autograd::AutogradContext* ctx) { return (tcnn_module*)ctx->saved_data.at("module").toInt(); }
 
 // reference modules.py:128-170: the first-order backward as a differentiable function (only taken when
 // the backward itself is recorded, create_graph=True), whose backward is Module::backward_backward_input
 struct ModuleBackward : public torch::autograd::Function<ModuleBackward> {
-	static torch::autograd::variable_list forward(torch::autograd::AutogradContext* ctx, int64_t module, c10::IValue native_ctx,
-	                                              double loss_scale, torch::Tensor doutput, torch::Tensor input, torch::Tensor params,
+	static torch::autograd::variable_list forward(torch::autograd::AutogradContext* ctx, int64_t module, c10::IValue owner,
+	                                              c10::IValue native_ctx, double loss_scale, torch::Tensor doutput, torch::Tensor input, torch::Tensor params,
 	                                              torch::Tensor output) {
 		tcnn_module* m = (tcnn_module*)module;
 		ctx->saved_data["module"] = module;
+		ctx->saved_data["owner"] = owner;
 		ctx->saved_data["native"] = native_ctx;
 		ctx->saved_data["loss_scale"] = loss_scale;
 		ctx->save_for_backward({input, params, doutput});
@@ -66,7 +71,7 @@ struct ModuleBackward : public torch::autograd::Function<ModuleBackward> {
 		const auto saved = ctx->get_saved_variables();
 		const torch::Tensor input = saved[0], params = saved[1], doutput_saved = saved[2];
 		const torch::Tensor dinput_grad = grads[0];
-		torch::autograd::variable_list none(7);
+		torch::autograd::variable_list none(8);
 		if (!dinput_grad.defined()) return none;
 		tcnn_module* m = module_of(ctx);
 		const double ls = ctx->saved_data.at("loss_scale").toDouble();
@@ -95,14 +100,15 @@ struct ModuleBackward : public torch::autograd::Function<ModuleBackward> {
 		}
 		if (dpar.defined()) dpar = dpar / ls;
 		if (din.defined()) din = din / ls;
-		// inputs: module, native_ctx, loss_scale, doutput, input, params, output
-		return {torch::Tensor(), torch::Tensor(), torch::Tensor(), ddout, din, dpar, torch::Tensor()};
+		// inputs: module, owner, native_ctx, loss_scale, doutput, input, params, output
+		return {torch::Tensor(), torch::Tensor(), torch::Tensor(), torch::Tensor(), ddout, din, dpar, torch::Tensor()};
 	}
 };
 
 // reference modules.py:91-126 (_module_function)
 struct ModuleFunction : public torch::autograd::Function<ModuleFunction> {
-	static torch::Tensor forward(torch::autograd::AutogradContext* ctx, int64_t module, torch::Tensor input, torch::Tensor params, double loss_scale) {
+	static torch::Tensor forward(torch::autograd::AutogradContext* ctx, int64_t module, c10::IValue owner, torch::Tensor input, torch::Tensor params,
+	                             double loss_scale) {
 		tcnn_module* m = (tcnn_module*)module;
 		ctx->set_materialize_grads(false);
 		TORCH_CHECK(input.scalar_type() == torch::kFloat && input.is_contiguous() && input.size(1) == (int64_t)tcnn_module_n_input_dims(m),
@@ -122,6 +128,7 @@ struct ModuleFunction : public torch::autograd::Function<ModuleFunction> {
 			nctx = c10::make_intrusive<NativeCtx>(c);
 		}
 		ctx->saved_data["module"] = module;
+		ctx->saved_data["owner"] = owner;
 		ctx->saved_data["native"] = nctx;
 		ctx->saved_data["loss_scale"] = loss_scale;
 		ctx->save_for_backward({input, params, out});
@@ -130,7 +137,7 @@ struct ModuleFunction : public torch::autograd::Function<ModuleFunction> {
 
 	static torch::autograd::variable_list backward(torch::autograd::AutogradContext* ctx, torch::autograd::variable_list grads) {
 		torch::Tensor doutput = grads[0];
-		torch::autograd::variable_list none(4);
+		torch::autograd::variable_list none(5);
 		if (!doutput.defined()) return none;
 		TORCH_CHECK(doutput.is_cuda(), "tinycudann: doutput must be a GPU tensor");
 		const auto saved = ctx->get_saved_variables();
@@ -148,16 +155,17 @@ struct ModuleFunction : public torch::autograd::Function<ModuleFunction> {
 			torch::Tensor gpar = ctx->needs_input_grad(1) ? torch::empty({(int64_t)tcnn_module_n_params(m)}, params.options()) : torch::Tensor();
 			check(tcnn_module_backward_scaled(m, stream_of(input), native(ctx), (uint32_t)B, (float*)ptr(gin), ptr(doutput), ptr(gpar),
 			                                  (const float*)ptr(input), ptr(output), ptr(params), (float)ls, 0));
-			return {torch::Tensor(), gin, gpar, torch::Tensor()};
+			return {torch::Tensor(), torch::Tensor(), gin, gpar, torch::Tensor()};
 		}
-		auto g = ModuleBackward::apply((int64_t)m, ctx->saved_data.at("native"), ls, doutput, input, params, output);
+		auto g = ModuleBackward::apply((int64_t)m, ctx->saved_data.at("owner"), ctx->saved_data.at("native"), ls, doutput, input, params, output);
 		auto nn = [](const torch::Tensor& t) { return t.dim() == 0 ? torch::Tensor() : t; };  // null_tensor_to_none
-		return {torch::Tensor(), nn(g[0]), nn(g[1]), torch::Tensor()};
+		return {torch::Tensor(), torch::Tensor(), nn(g[0]), nn(g[1]), torch::Tensor()};
 	}
 };
 
-torch::Tensor module_apply(int64_t module, torch::Tensor input, torch::Tensor params, double loss_scale) {
-	return ModuleFunction::apply(module, input, params, loss_scale);
+// owner: the Python object whose collection destroys `module` (called with the GIL held, as every pybind function)
+torch::Tensor module_apply(int64_t module, py::object owner, torch::Tensor input, torch::Tensor params, double loss_scale) {
+	return ModuleFunction::apply(module, c10::IValue(c10::ivalue::ConcretePyObjectHolder::create(std::move(owner))), input, params, loss_scale);
 }
 
 }  // namespace
@@ -166,5 +174,5 @@ TORCH_LIBRARY(tcnn_mi355x, m) { m.class_<NativeCtx>("NativeCtx"); }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
 	m.doc() = "tinycudann (MI355X) torch autograd node in C++ over the engine's C-ABI";
-	m.def("module_apply", &module_apply, "tinycudann.Module forward with its C++ autograd node (handle, input, params, loss_scale)");
+	m.def("module_apply", &module_apply, "tinycudann.Module forward with its C++ autograd node (handle, its owner, input, params, loss_scale)");
 }

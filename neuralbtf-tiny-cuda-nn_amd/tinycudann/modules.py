@@ -196,7 +196,7 @@ class _NativeModule:
         dL_dinput = torch.empty_like(input) if input.requires_grad else None
         dL_dparams = torch.empty(self.n_params(), dtype=_torch_precision(self.param_precision()), device=input.device) if params.requires_grad else None
         dL_doutput = dL_doutput.to(_torch_precision(self.output_precision())).contiguous()
-        L.check(L.lib().tcnn_module_backward(self.h, _stream(), ctx.h, B, _ptr(dL_dinput), _ptr(dL_doutput),
+        L.check(L.lib().tcnn_module_backward(self.h, _stream(input), ctx.h, B, _ptr(dL_dinput), _ptr(dL_doutput),
                                              _ptr(dL_dparams), _ptr(input), _ptr(output), _ptr(params)))
         return dL_dinput, dL_dparams
 
@@ -213,7 +213,7 @@ class _NativeModule:
             dL_ddLdinput = dL_ddLdinput.to(torch.float32).contiguous()
             dout = dL_doutput.detach().to(_torch_precision(self.output_precision())).contiguous()
             L.check(L.lib().tcnn_module_backward_backward_input(
-                self.h, _stream(), ctx.h, B, _ptr(dL_ddLdinput), _ptr(input),
+                self.h, _stream(input), ctx.h, B, _ptr(dL_ddLdinput), _ptr(input),
                 _ptr(dout) if (params.requires_grad or input.requires_grad) else None,
                 _ptr(dL_dparams), _ptr(dL_ddLdoutput), _ptr(dL_dinput), _ptr(params)))
         return dL_ddLdoutput, dL_dparams, dL_dinput
@@ -331,7 +331,7 @@ class Module(torch.nn.Module):
         if not params.is_contiguous():
             params = params.contiguous()
         if _EXT is not None:
-            output = _EXT.module_apply(self.native_tcnn_module.h, x_padded, params, float(self.loss_scale))
+            output = _EXT.module_apply(self.native_tcnn_module.h, self.native_tcnn_module, x_padded, params, float(self.loss_scale))
         else:
             output = _module_function.apply(self.native_tcnn_module, x_padded, params, self.loss_scale)
         if batch_size == padded and output.shape[1] == self.n_output_dims:

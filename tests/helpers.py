@@ -151,6 +151,15 @@ def assert_within_fp16_ulps(got, ref, n_ulp=4):
     assert err <= n_ulp * ulp, (err, ulp, scale)
 
 
+def wgrad_per_element_bound(ref, mag, ulps=8, fp16_out=False, floor_rel=1e-6):
+    """the per-element bound of assert_wgrad_per_element (derived there), as an array"""
+    ref, mag = np.asarray(ref, np.float64), np.asarray(mag, np.float64)
+    bound = ulps * 2.0 ** -10 * mag + floor_rel * np.abs(ref).max()
+    if fp16_out:
+        bound += 2.0 ** -11 * np.abs(ref) + 2.0 ** -25  # fp16 rounding (subnormals: half the smallest step)
+    return bound
+
+
 def assert_wgrad_per_element(got, ref, mag, ulps=8, fp16_out=False, floor_rel=1e-6):
     """Per-element bound of an MLP weight gradient dW = sum_i delta_i a_i. Between the HIP kernels
     (fp32 MFMA) and the oracle (fp32 CPU order) a term's fp16 activation or delta can round to the
@@ -159,10 +168,7 @@ def assert_wgrad_per_element(got, ref, mag, ulps=8, fp16_out=False, floor_rel=1e
     fp16), mag = sum_i |delta_i a_i| (oracle.mlp_wgrad_magnitude). The fp32 summation error of either
     side (K * 2^-24 relative) is far below this."""
     got, ref, mag = (np.asarray(v, np.float64) for v in (got, ref, mag))
-    bound = ulps * 2.0 ** -10 * mag + floor_rel * np.abs(ref).max()
-    if fp16_out:
-        bound += 2.0 ** -11 * np.abs(ref) + 2.0 ** -25  # fp16 rounding (subnormals: half the smallest step)
-    r = np.abs(got - ref) / bound
+    r = np.abs(got - ref) / wgrad_per_element_bound(ref, mag, ulps, fp16_out, floor_rel)
     k = int(np.argmax(r))
     assert r[k] <= 1.0, (float(r[k]), k, got[k], ref[k], mag[k])
     return float(r[k])

@@ -23,7 +23,7 @@ restated here once, in check_output / check_wgrad / check_dinput / aggregate_bar
 """
 import numpy as np
 
-from helpers import assert_within_fp16_ulps, assert_wgrad_per_element, rel_err
+from helpers import assert_within_fp16_ulps, assert_wgrad_per_element, rel_err, wgrad_per_element_bound
 
 ACTIVATIONS = ["None", "ReLU", "LeakyReLU", "Exponential", "Sigmoid", "Squareplus", "Softplus", "Tanh"]
 K_ACT = 10.0  # common_device.h:100
@@ -188,6 +188,31 @@ def check_wgrad(got_flat, ref, fp16_out=True):
             raise AssertionError((name,) + tuple(e.args)) from None
         off += n
     assert off == got_flat.size, (off, got_flat.size)
+    return ratios
+
+
+def check_wgrad_sum(got_flat, refs, bar, per_element=True):
+    """The weight gradient torch accumulates when one module is called several times in one graph: the
+    fp32 sum of the calls' fp16 gradients, against the sum of the calls' float64 references. Per element and
+    per matrix the bound is the sum of the calls' own bounds (check_wgrad's, fp16 gradient) plus the rounding
+    of each fp32 addition, 2^-24 of the |reference| sums; relative L2 of the whole sum within bar (that alone with per_element=False:
+    unfiltered samples of a branchy network). Returns {matrix name: worst ratio, "agg_w": relative L2}."""
+    got_flat = np.asarray(got_flat, np.float64)
+    ratios, off = {}, 0
+    for k, name in enumerate(matrix_names(len(refs[0]["wgrad"]) - 1) if per_element else []):
+        rs = [r["wgrad"][k].ravel() for r in refs]
+        bound = sum(wgrad_per_element_bound(r, ref["mag_w"][k].ravel(), ulps=ULPS, fp16_out=True) for r, ref in zip(rs, refs))
+        bound = bound + (len(refs) - 1) * 2.0 ** -24 * sum(np.abs(r) for r in rs)
+        n = rs[0].size
+        q = np.abs(got_flat[off:off + n] - sum(rs)) / bound
+        j = int(np.argmax(q))
+        assert q[j] <= 1.0, (name, float(q[j]), j, got_flat[off + j], float(sum(rs)[j]))
+        ratios[name] = float(q[j])
+        off += n
+    assert off == got_flat.size or not per_element, (off, got_flat.size)
+    flat = sum(np.concatenate([w.ravel() for w in r["wgrad"]]) for r in refs)
+    ratios["agg_w"] = rel_err(got_flat, flat)
+    assert ratios["agg_w"] <= bar, ("wgrad rel L2", ratios["agg_w"], bar)
     return ratios
 
 

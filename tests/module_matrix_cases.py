@@ -118,6 +118,28 @@ def torch_cases():
     return c
 
 
+def graph_case(name, B=256):
+    """the networks of tests/test_gpu_torch_graphs.py (multi-call autograd graphs on the torch front end), at
+    batch size B: T OneBlob 16 + W32/H2 (tile kernel), I 5 inputs + W64/H2 ReLU (tile, branchy), G grid + W64/H2
+    (register kernel without dL/dinput, tile with it), L 16 inputs + W48/H1 CutlassMLP (layered)"""
+    if name == "T":
+        return Case("graph", "oneblob16", 32, 2, "None", B=B)
+    if name == "I":
+        return Case("graph", "identity5", 64, 2, "ReLU", B=B)
+    if name == "G":
+        return Case("graph", "grid", 64, 2, "None", B=B, nodx="register", dx="tile")
+    assert name == "L", name
+    return Case("graph", "identity", 48, 1, "None", otype="CutlassMLP", B=B, nodx="layered", dx="layered")
+
+
+def graph_id(name, want_dx):
+    return graph_case(name).id + ("-dx" if want_dx else "-nodx")
+
+
+# B.1 of test_gpu_torch_graphs.py: (network, dL/dx requested); two calls each, B = 256 (seed 0) and 300 (seed 1)
+GRAPH_TWICE = [("T", True), ("G", True), ("G", False), ("L", True), ("I", True)]
+GRAPH_TWICE_B = (256, 300)
+
 CASES = _cases()
 N_CU_CPU = 256  # the MI355X's compute units: the batch the CPU proof runs the uneven cases at
 ALL_CPU_CASES = CASES + uneven_cases(N_CU_CPU) + torch_cases()
@@ -302,6 +324,21 @@ def reference(case, params16, enc16, dout16):
     return R.mlp_reference(case.W, case.IN, case.NH, case.OUTP, case.act, case.out_act, params16[:case.n_mlp], enc16, dout16)
 
 
+def torch_reference(case, params16, enc16, dout16, loss_scale):
+    """reference() as the torch binding computes it: the binding multiplies dL/dy by its loss scale (128, exact
+    in fp16 for |dL/dy| <= 1) and divides the gradients by it, so the reference runs on loss_scale * dL/dy and
+    its gradients and magnitudes are divided by loss_scale (powers of two commute with every rounding above
+    the subnormals; the bounds' 2^-25 covers those)."""
+    s = float(loss_scale)
+    dout_s = np.array(dout16, np.uint16)
+    dout_s[:, :case.n_out] = O.f2h(O.h2f(dout_s[:, :case.n_out]) * np.float32(s))
+    ref = reference(case, params16, enc16, dout_s)
+    for k in ("wgrad", "mag_w"):
+        ref[k] = [m / s for m in ref[k]]
+    ref["dinput"], ref["mag_in"] = ref["dinput"] / s, ref["mag_in"] / s
+    return ref
+
+
 def oracle_run(case, params16, enc16, dout16, n_threads=4):
     """the fp32 CPU oracle on the same rows: (out, flat weight gradient, dL/d(encoding)) as float64"""
     p = params16[:case.n_mlp]
@@ -379,24 +416,36 @@ RATIOS_HEADER = """\
 """
 
 
-def merge_ratios(gpu_path, oracle_path, out_path):
-    """profiles/module_matrix_ratios.txt from the JSON lines the two test modules wrote: one line per GPU
-    run, each figure next to the oracle's for the same case, batch size and kind (per_element / aggregate)"""
+GRAPH_RATIOS_HEADER = """\
+# Torch front end, multi-call autograd graphs (tests/test_gpu_torch_graphs.py): worst ratio |got - float64 reference|
+# / bound per matrix and for dL/dinput, relative L2 for agg_* / *_rel (agg_w: the summed weight gradient, grid_rel /
+# dx_rel: the grid's own gradients; g_rel / xgrad_rel / wgrad_rel / pgrad_rel: the eikonal pattern's). Kinds are
+# graph-<test>-<node>. Each entry: MI355X / fp32 CPU oracle on the same inputs (tests/test_mlp_reference.py, the
+# twice-in-one-graph cases only). Both test modules append JSON lines under TCNN_MATRIX_RATIOS=<file>;
+# PYTHONPATH=. python tests/module_matrix_cases.py <gpu lines> <oracle lines> <this file> graph merges them.
+"""
+
+
+def merge_ratios(gpu_path, oracle_path, out_path, header=None):
+    """profiles/module_matrix_ratios.txt (profiles/torch_graph_ratios.txt with header=GRAPH_RATIOS_HEADER) from
+    the JSON lines the two test modules wrote: one line per GPU run, each figure next to the oracle's for the
+    same case, batch size and kind (per_element / aggregate; graph-<test>, the GPU's kind without its last part)"""
     import json
+    header = RATIOS_HEADER if header is None else header
 
     def lines(path):
         return [json.loads(ln) for ln in open(path) if ln.strip()]
 
     fmt = lambda v: "-" if v is None else f"{v:.3g}"  # noqa: E731
     oracle = {(e["case"], e["B"], e["kind"]): e["ratios"] for e in lines(oracle_path)}
-    worst, out = [], [RATIOS_HEADER]
+    worst, out = [], [header]
     for e in lines(gpu_path):
         kind = e["kind"].split("-")[0]
-        ref = oracle.get((e["case"], e["B"], kind), {})
+        ref = oracle.get((e["case"], e["B"], e["kind"].rsplit("-", 1)[0]), oracle.get((e["case"], e["B"], kind), {}))
         cells = []
         for k, v in e["ratios"].items():
             cells.append(f"{k}={fmt(v)}/{fmt(ref.get(k))}")
-            if kind == "per_element" and v is not None and not k.startswith("agg_"):
+            if kind in ("per_element", "graph") and v is not None and not (k.startswith("agg_") or k.endswith("_rel")):
                 worst.append((v, f"{e['case']} [{e['kind']}] {k} {fmt(v)} (oracle {fmt(ref.get(k))})"))
         out.append(f"{e['case']} [{e['kind']}] " + " ".join(cells) + "\n")
     worst.sort(key=lambda t: -t[0])
@@ -407,4 +456,4 @@ def merge_ratios(gpu_path, oracle_path, out_path):
 
 if __name__ == "__main__":
     import sys
-    merge_ratios(*sys.argv[1:4])
+    merge_ratios(*sys.argv[1:4], header=GRAPH_RATIOS_HEADER if sys.argv[4:5] == ["graph"] else None)

@@ -249,8 +249,7 @@ def test_torch_front_end(gpu, case):
     against the float64 reference of the B real rows. Module.forward pads B = 300 to 512 rows and slices the
     output to n_output_dims columns; the padded rows and columns must contribute nothing. The binding
     multiplies dL/dy by its loss scale (128, exact in fp16 for |c| <= 1) and divides the gradients by it:
-    the reference runs on 128 c and is divided by 128 (powers of two commute with every rounding above the
-    subnormals; the bound's 2^-25 covers those)."""
+    the reference runs on 128 c and is divided by 128 (module_matrix_cases.torch_reference)."""
     torch = gpu[0]
     import tinycudann as tcnn
     if case.enc_cfg is None:
@@ -276,12 +275,7 @@ def test_torch_front_end(gpu, case):
         assert out.shape == (case.B, case.n_out) and out.dtype == torch.float16
         (out.float() * torch.from_numpy(O.h2f(c16)).cuda()).sum().backward()
         torch.cuda.synchronize()
-        dout_s = dout.copy()
-        dout_s[:, :case.n_out] = O.f2h(O.h2f(c16) * np.float32(s))
-        ref = C.reference(case, p16, enc, dout_s)
-        for k in ("wgrad", "mag_w"):
-            ref[k] = [m / s for m in ref[k]]
-        ref["dinput"], ref["mag_in"] = ref["dinput"] / s, ref["mag_in"] / s
+        ref = C.torch_reference(case, p16, enc, dout, s)
         got_out = np.zeros((case.B, case.OUTP))
         got_out[:, :case.n_out] = out.detach().float().cpu().numpy()
         grad = model.params.grad.cpu().numpy().astype(np.float64)

@@ -18,6 +18,7 @@ import pytest
 
 import mlp_reference as R
 import module_matrix_cases as C
+from helpers import rel_err
 
 PAIRS = [(a, o) for a in R.ACTIVATIONS for o in R.ACTIVATIONS]
 
@@ -150,6 +151,14 @@ def _dump(case, kind, ratios):
             f.write(json.dumps({"case": case.id, "B": case.B, "side": "oracle", "kind": kind, "ratios": ratios}) + "\n")
 
 
+def _dump_graph(case, name, want_dx, ratios):
+    path = os.environ.get("TCNN_MATRIX_RATIOS")
+    if path:
+        with open(path, "a") as f:
+            f.write(json.dumps({"case": C.graph_id(name, want_dx), "B": "+".join(map(str, C.GRAPH_TWICE_B)), "side": "oracle",
+                                "kind": "graph-twice", "ratios": ratios}) + "\n")
+
+
 @pytest.mark.parametrize("case", C.ALL_CPU_CASES, ids=[c.id for c in C.ALL_CPU_CASES])
 def test_oracle_within_every_bound(case):
     """the fp32 oracle against the float64 reference, the GPU's assertions; branchy cases: per element on
@@ -167,3 +176,34 @@ def test_oracle_within_every_bound(case):
         ref = C.reference(case, p16, enc, dout)
         out, wg, denc = C.oracle_run(case, p16, enc, dout, n_threads=8)
         _dump(case, "aggregate", C.check_against_reference(case, ref, out, wg, denc, False, fp16_out=False))
+
+
+@pytest.mark.parametrize("name,want_dx", C.GRAPH_TWICE, ids=[f"{n}-{'dx' if d else 'nodx'}" for n, d in C.GRAPH_TWICE])
+def test_oracle_sum_of_two_calls_within_bound(name, want_dx):
+    """The CPU proof of tests/test_gpu_torch_graphs.py's twice-in-one-graph bound: one module called at B = 256
+    (draw seed 0) and B = 300 (seed 1), the fp32 oracle per call on 128 dL/dy, its gradient rounded to fp16 and
+    divided by 128 in fp16 as the binding returns it, the two summed in fp32 as torch accumulates them. The sum
+    passes mlp_reference.check_wgrad_sum against the float64 references (per element and aggregate; the ReLU
+    network on unfiltered draws aggregate only), and each call passes the single-call checks."""
+    from oracle import oracle as O
+    s, total, refs, ratios = 128.0, None, [], {}
+    for seed, B in enumerate(C.GRAPH_TWICE_B):
+        case = C.graph_case(name, B)
+        p16 = C.scale_params16(case, C.host_params32(case))
+        _, enc, dout = C.draw(case, p16, filtered=False, seed=seed)
+        ref = C.torch_reference(case, p16, enc, dout, s)
+        dout_s = dout.copy()
+        dout_s[:, :case.n_out] = O.f2h(O.h2f(dout[:, :case.n_out]) * np.float32(s))
+        out, wg, denc = C.oracle_run(case, p16, enc, dout_s, n_threads=8)
+        g16 = O.h2f(O.f2h(O.h2f(O.f2h(wg.astype(np.float32))) / np.float32(s)))  # fp16(fp16(g) / s)
+        total = g16 if total is None else total + g16  # float32 + float32
+        R.check_output(out[:, :case.n_out], ref["out"][:, :case.n_out])
+        if case.branchy:
+            ratios[f"agg_in{seed + 1}"] = rel_err(denc / s, ref["dinput"])
+            assert ratios[f"agg_in{seed + 1}"] <= R.aggregate_bar(case.W, case.NH, case.out_act)
+        else:
+            ratios[f"dinput{seed + 1}"] = R.check_dinput(denc / s, ref["dinput"], ref["mag_in"])
+        refs.append(ref)
+    assert total.dtype == np.float32
+    ratios.update(R.check_wgrad_sum(total, refs, R.aggregate_bar(case.W, case.NH, case.out_act), per_element=not case.branchy))
+    _dump_graph(case, name, want_dx, ratios)
