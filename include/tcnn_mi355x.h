@@ -123,6 +123,8 @@ int tcnn_module_set_max_level_gpu(tcnn_module* m, const float* max_level_per_poi
 uint32_t tcnn_module_n_input_dims(const tcnn_module* m);
 uint32_t tcnn_module_n_output_dims(const tcnn_module* m); /* padded width (cpp_api.cu:130) */
 uint64_t tcnn_module_n_params(const tcnn_module* m);
+/* of which the network's (matrix) parameters, which come first: 0 for an encoding module */
+uint64_t tcnn_module_n_network_params(const tcnn_module* m);
 /* the module's own precision (TCNN_PRECISION_*): Fp32 for an encoding created with it, else Fp16 */
 int tcnn_module_param_precision(const tcnn_module* m);
 int tcnn_module_output_precision(const tcnn_module* m);
@@ -250,6 +252,56 @@ int tcnn_trainer_loss_value(tcnn_trainer* t, void* stream, float* out);
  * [n x stride] (each already divided by n * dims); padded columns get zeros. Returns once the work has finished. */
 int tcnn_loss_evaluate(const char* otype, void* stream, uint32_t n, uint32_t stride, uint32_t dims, float loss_scale,
                        const void* predictions16, const float* targets, float* values, void* gradients16, const float* data_pdf);
+/* ---- the torch front end's loss and optimizer objects (tinycudann.Loss, tinycudann.optim.Adam): the engine's
+ * losses and Adam on the caller's tensors. Every call queues its kernels on `stream` and returns: nothing is
+ * allocated, nothing is read back and the stream is not synchronised. ---- */
+/* The engine's code of a loss otype (case-insensitive) for the two calls below; -1 with tcnn_last_error
+ * naming the nine otypes for any other. */
+int tcnn_loss_type(const char* otype);
+/* Floats of workspace tcnn_loss_forward needs for n x dims predictions (its per-workgroup partial sums). */
+uint32_t tcnn_loss_workspace_floats(uint64_t n, uint32_t dims);
+/* *value (device, fp32) = the loss: the sum over the n x dims elements of the per-element values, each already
+ * divided by n * dims, added in a fixed order (per-workgroup partials in `workspace`, then one workgroup over
+ * the partials; a single workgroup's worth of elements takes one kernel) -- no atomics, so equal inputs give
+ * equal bits. predictions: fp16, or fp32 with predictions_fp32 != 0, n rows of row_stride elements of which the
+ * first dims are read (any row_stride >= dims; only those columns are touched); targets and data_pdf (or NULL):
+ * fp32 [n x dims] contiguous. 1 <= dims <= 16 (RelativeL2Luminance: dims >= 3; it reads columns 0..2, and
+ * 3..5 when dims >= 6), n * dims < 2^32. */
+int tcnn_loss_forward(int loss_type, void* stream, uint64_t n, uint32_t dims, const void* predictions, int predictions_fp32,
+                      uint64_t row_stride, const float* targets, const float* data_pdf, float* workspace, uint32_t workspace_floats,
+                      float* value);
+/* gradients [n x dims] contiguous, in the predictions' type = dL/dpredictions as tcnn_loss_evaluate computes
+ * it, with the loss scale read from device memory: *grad_output * (...) / (n * dims) in the reference's
+ * operation order, normalisers held fixed; fp16 rounded once from the fp32 result, fp32 stored as it is (fp32
+ * predictions are used unrounded). One kernel. */
+int tcnn_loss_backward(int loss_type, void* stream, uint64_t n, uint32_t dims, const void* predictions, int predictions_fp32,
+                       uint64_t row_stride, const float* targets, const float* data_pdf, const float* grad_output, void* gradients);
+/* Adam's hyper-parameters under the reference's names, with its defaults in the comments (adam.h:235-283). */
+typedef struct tcnn_adam_options {
+	float learning_rate;                   /* 1e-3 */
+	float beta1, beta2, epsilon;           /* 0.9, 0.999, 1e-8 */
+	float l2_reg;                          /* 1e-8; matrix parameters only */
+	float relative_decay, absolute_decay;  /* 0, 0 */
+	float clipping_magnitude;              /* 0: none */
+	float non_matrix_learning_rate_factor; /* 1 */
+	int adabound;                          /* 0 */
+	int optimize_matrix_params;            /* 1 */
+	int optimize_non_matrix_params;        /* 1 */
+} tcnn_adam_options;
+/* One Adam step (adam.h:47-119) on a caller's buffers, in one kernel: n fp32 parameters, of which the first
+ * n_matrix are matrix parameters (l2_reg applies to them; a non-matrix parameter whose gradient is zero is
+ * skipped and keeps its step count; non_matrix_learning_rate_factor applies to the rest), their gradients as
+ * they are (fp32, or fp16 with gradients_fp16 != 0: no loss scale, no rounding), both moments (fp32) and the
+ * per-parameter step counts (uint32), all device pointers aligned to 16 bytes. step: the optimizer's own count
+ * after this step (AdaBound's bounds). bias_factors (device, or NULL): sqrt(1 - beta2^t) / (1 - beta1^t) at
+ * [t - 1] for t = 1 .. n_bias_factors as tcnn_adam_bias_factors computes them; a parameter whose step count is
+ * beyond the table computes its factor on the device. n < 2^32. */
+int tcnn_adam_step_buffers(void* stream, const tcnn_adam_options* options, uint64_t n, uint64_t n_matrix, uint32_t step, float* params,
+                           const void* gradients, int gradients_fp16, float* first_moments, float* second_moments, uint32_t* param_steps,
+                           const float* bias_factors, uint32_t n_bias_factors);
+/* out[k] (HOST, n floats) = Adam's bias-correction factor of step first_step + k, by the C library's powf and
+ * sqrtf: the table the trainer's own Adam reads (a device powf differs in the last bit for some steps). */
+int tcnn_adam_bias_factors(float beta1, float beta2, uint32_t first_step, uint32_t n, float* out);
 /* Device pointer to the last step's loss sum (fp32 scalar), for graph-friendly readback. */
 const float* tcnn_trainer_loss_device(tcnn_trainer* t);
 /* network->inference(stream, input, output fp32 [n x n_out]) (object.h:147-176) */

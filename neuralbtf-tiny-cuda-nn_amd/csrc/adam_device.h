@@ -12,13 +12,11 @@ __device__ __forceinline__ float adam_bias_factor(const AdamArgs& a, uint32_t st
 	return sqrtf(1.0f - powf(a.beta2, (float)st)) / (1.0f - powf(a.beta1, (float)st));
 }
 
-// Adam on register values of parameter i (fp32 gradient sum gsum); returns false when the
-// parameter is skipped (reference adam.h:75-82: frozen class, or a zero non-matrix gradient).
-__device__ __forceinline__ bool adam_core(const AdamArgs& a, uint32_t i, float gsum, _Float16& g16, float& w, float& m1, float& m2,
-                                          uint32_t& step) {
-	g16 = f16_rn(gsum * a.grad_scale);
-	// x / 2^k is exact, so a power-of-two loss scale (128) becomes a multiply
-	float gradient = a.inv_loss_scale != 0.0f ? (float)g16 * a.inv_loss_scale : (float)g16 / a.loss_scale;
+// Adam on register values of parameter i from its unscaled fp32 gradient (adam.h:75-119); returns
+// false when the parameter is skipped (adam.h:75-82: frozen class, or a zero non-matrix gradient).
+// The one statement of the update: the engine's kernels reach it through adam_core, the torch
+// optimizer's kernel (k_adam_torch, optimizers.hip) directly.
+__device__ __forceinline__ bool adam_tail(const AdamArgs& a, uint32_t i, float gradient, float& w, float& m1, float& m2, uint32_t& step) {
 	if (i >= a.n_matrix) {
 		if (!a.opt_nonmatrix || gradient == 0.0f) return false;
 	} else {
@@ -39,6 +37,16 @@ __device__ __forceinline__ bool adam_core(const AdamArgs& a, uint32_t i, float g
 	if (a.clip != 0.0f) nw = fminf(fmaxf(nw, -a.clip), a.clip);
 	w = nw;
 	return true;
+}
+
+// The engine's head of the update: the fp32 gradient sum gsum rounded to the fp16 gradient g16 and
+// the loss scale divided out of it, then adam_tail.
+__device__ __forceinline__ bool adam_core(const AdamArgs& a, uint32_t i, float gsum, _Float16& g16, float& w, float& m1, float& m2,
+                                          uint32_t& step) {
+	g16 = f16_rn(gsum * a.grad_scale);
+	// x / 2^k is exact, so a power-of-two loss scale (128) becomes a multiply
+	const float gradient = a.inv_loss_scale != 0.0f ? (float)g16 * a.inv_loss_scale : (float)g16 / a.loss_scale;
+	return adam_tail(a, i, gradient, w, m1, m2, step);
 }
 
 // Updates parameter i in memory; returns the parameter's fp16 value afterwards.

@@ -5,9 +5,13 @@
 #include "debug_grid_bwd.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
+#include <limits>
 #include <mutex>
 
+#include "loss_torch.h"
+#include "optimizers.h"
 #include "runtime.h"
 
 using namespace tcnn_amd;
@@ -114,6 +118,7 @@ struct ModuleBase {
 	virtual uint32_t n_input_dims() const = 0;
 	virtual uint32_t n_output_dims() const = 0;
 	virtual uint64_t n_params() const = 0;
+	virtual uint64_t n_network_params() const { return 0; }  // the matrix parameters, which come first
 	virtual void initialize_params(uint64_t seed, float* params_fp32, float scale) = 0;
 	virtual json hyperparams() const = 0;
 	virtual std::string name() const = 0;
@@ -207,6 +212,7 @@ struct ModuleNWIE : ModuleBase {
 	uint32_t n_input_dims() const override { return model.n_input_dims; }
 	uint32_t n_output_dims() const override { return model.mlp.padded_output; }
 	uint64_t n_params() const override { return model.n_params(); }
+	uint64_t n_network_params() const override { return model.mlp.n_params(); }
 	void initialize_params(uint64_t seed, float* p, float scale) override {
 		Pcg32 rng{seed};
 		std::vector<float> host(n_params());
@@ -488,6 +494,7 @@ int tcnn_module_set_max_level_gpu(tcnn_module* m, const float* max_level_per_poi
 uint32_t tcnn_module_n_input_dims(const tcnn_module* m) { return m->m->n_input_dims(); }
 uint32_t tcnn_module_n_output_dims(const tcnn_module* m) { return m->m->n_output_dims(); }
 uint64_t tcnn_module_n_params(const tcnn_module* m) { return m->m->n_params(); }
+uint64_t tcnn_module_n_network_params(const tcnn_module* m) { return m->m->n_network_params(); }
 int tcnn_module_param_precision(const tcnn_module* m) { return m->m->precision(); }
 int tcnn_module_output_precision(const tcnn_module* m) { return m->m->precision(); }
 int tcnn_module_initialize_params(tcnn_module* m, uint64_t seed, float* p, float scale) {
@@ -675,6 +682,75 @@ int tcnn_loss_evaluate(const char* otype, void* stream, uint32_t n, uint32_t str
 		part.reserve((size_t)relative_l2_n_blocks(n, stride) * sizeof(float));
 		launch_relative_l2_partial((hipStream_t)stream, n, stride, dims, loss_scale, pred16, target, grads16, part.as<float>(), (uint32_t)type, pdf,
 		                           values);
+	});
+}
+int tcnn_loss_type(const char* otype) {
+	int type = -1;
+	guard([&] {
+		TCNN_CHECK(otype != nullptr, "loss: null otype");
+		type = loss_type_from_otype(otype);
+		TCNN_CHECK(type >= 0, std::string("Loss '") + otype + "' is not implemented by the MI355X engine (" + loss_otype_list() + ")");
+	});
+	return type;
+}
+uint32_t tcnn_loss_workspace_floats(uint64_t n, uint32_t dims) { return loss_torch_n_partials(n, dims); }
+int tcnn_loss_forward(int loss_type, void* stream, uint64_t n, uint32_t dims, const void* pred, int pred_f32, uint64_t row_stride,
+                      const float* target, const float* pdf, float* workspace, uint32_t workspace_floats, float* value) {
+	return guard([&] {
+		launch_loss_torch_value((hipStream_t)stream, (uint32_t)loss_type, n, dims, pred, pred_f32 != 0, row_stride, target, pdf, workspace,
+		                        workspace_floats, value);
+	});
+}
+int tcnn_loss_backward(int loss_type, void* stream, uint64_t n, uint32_t dims, const void* pred, int pred_f32, uint64_t row_stride,
+                       const float* target, const float* pdf, const float* grad_output, void* gradients) {
+	return guard([&] {
+		launch_loss_torch_grad((hipStream_t)stream, (uint32_t)loss_type, n, dims, pred, pred_f32 != 0, row_stride, target, pdf, grad_output,
+		                       gradients);
+	});
+}
+int tcnn_adam_step_buffers(void* stream, const tcnn_adam_options* o, uint64_t n, uint64_t n_matrix, uint32_t step, float* params,
+                           const void* grad, int grad_f16, float* m1, float* m2, uint32_t* steps, const float* bias_factors,
+                           uint32_t n_bias_factors) {
+	return guard([&] {
+		TCNN_CHECK(o != nullptr, "adam_step_buffers: null options");
+		TCNN_CHECK(n < (1ull << 32), "adam_step_buffers: a parameter tensor must hold fewer than 2^32 elements");
+		if (!n) return;
+		TCNN_CHECK(params && grad && m1 && m2 && steps, "adam_step_buffers: null parameters, gradients or state");
+		for (const void* p : {(const void*)params, grad, (const void*)m1, (const void*)m2, (const void*)steps})
+			TCNN_CHECK((uintptr_t)p % 16 == 0, "adam_step_buffers: parameters, gradients and state must be aligned to 16 bytes");
+		AdamArgs a{};
+		a.n = (uint32_t)n;
+		a.n_matrix = (uint32_t)std::min<uint64_t>(n_matrix, n);
+		a.loss_scale = a.grad_scale = a.inv_loss_scale = 1.0f;  // unused: the gradient is taken as it is
+		a.lr = o->learning_rate;
+		a.beta1 = o->beta1;
+		a.beta2 = o->beta2;
+		a.eps = o->epsilon;
+		a.l2_reg = o->l2_reg;
+		a.rel_decay = o->relative_decay;
+		a.abs_decay = o->absolute_decay;
+		a.clip = o->clipping_magnitude;
+		a.nonmat_lr_factor = o->non_matrix_learning_rate_factor;
+		a.lower_lr_bound = 0.0f;
+		a.upper_lr_bound = std::numeric_limits<float>::max();
+		if (o->adabound) {  // adam.h:156-159, as TrainerHost::adam_args
+			a.lower_lr_bound = 0.1f - 0.1f / ((1 - o->beta2) * (float)step + 1);
+			a.upper_lr_bound = 0.1f + 0.1f / ((1 - o->beta2) * (float)step);
+		}
+		a.opt_matrix = o->optimize_matrix_params;
+		a.opt_nonmatrix = o->optimize_non_matrix_params;
+		a.factor_table = bias_factors;
+		a.factor_n = bias_factors ? n_bias_factors : 0u;
+		launch_adam_torch((hipStream_t)stream, a, params, grad, grad_f16 != 0, m1, m2, steps);
+	});
+}
+int tcnn_adam_bias_factors(float beta1, float beta2, uint32_t first_step, uint32_t n, float* out) {
+	return guard([&] {
+		TCNN_CHECK(out != nullptr || n == 0, "adam_bias_factors: null result pointer");
+		for (uint32_t k = 0; k < n; ++k) {  // as TrainerHost::adam_args_table
+			const float t = (float)(first_step + k);
+			out[k] = std::sqrt(1.0f - std::pow(beta2, t)) / (1.0f - std::pow(beta1, t));
+		}
 	});
 }
 const float* tcnn_trainer_loss_device(tcnn_trainer* t) { return t->t->d_loss.as<float>(); }

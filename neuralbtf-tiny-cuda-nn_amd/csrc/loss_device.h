@@ -46,12 +46,21 @@ __device__ __forceinline__ float loss_luminance(float r, float g, float b) {
 constexpr int LOSS_ANY = -1;
 constexpr int LOSS_L2_FAMILY = -2;
 
-// One output element: the loss value (already divided by n_total) and the loss-scaled fp16 gradient.
+// One output element: the loss value (already divided by n_total) and the loss-scaled gradient.
 // PDF: data_pdf is present (false: pdf = 1, and the divisions by it, exact, are left out).
 // lum is read for RelativeL2Luminance only.
-template <bool PDF, int LOSS = LOSS_ANY>
+// G: the type the gradient is stored in -- _Float16 (rounded once from the fp32 result) or float (the
+// fp32 result itself: the torch loss on fp32 predictions, loss_torch.hip).
+template <typename G>
+__device__ __forceinline__ G loss_grad_store(float g);
+template <>
+__device__ __forceinline__ _Float16 loss_grad_store<_Float16>(float g) { return f16_rn(g); }
+template <>
+__device__ __forceinline__ float loss_grad_store<float>(float g) { return g; }
+
+template <bool PDF, int LOSS = LOSS_ANY, typename G = _Float16>
 __device__ __forceinline__ void loss_eval(uint32_t type_rt, float p, float t, float pdf, float n_total, float loss_scale, float lum,
-                                          float& value, _Float16& grad) {
+                                          float& value, G& grad) {
 	const uint32_t type = LOSS >= 0 ? (uint32_t)LOSS : type_rt;
 	const float d = p - t;
 	if (LOSS == LOSS_L2_FAMILY || type <= LOSS_RELATIVE_L2_LUMINANCE) {  // relative_l2.h:66-75, l2.h:66-74, relative_l2_luminance.h:66-86
@@ -60,18 +69,18 @@ __device__ __forceinline__ void loss_eval(uint32_t type_rt, float p, float t, fl
 		else pse = type == LOSS_L2 ? 1.0f : type == LOSS_RELATIVE_L2 ? __builtin_fmaf(p, p, 0.01f) : __builtin_fmaf(lum, lum, 0.01f);
 		if constexpr (PDF) {
 			value = d * d / pse / pdf / n_total;
-			grad = f16_rn(loss_scale * (2.0f * d / pse / pdf) / n_total);
+			grad = loss_grad_store<G>(loss_scale * (2.0f * d / pse / pdf) / n_total);
 		} else {
 			value = d * d / pse / n_total;
-			grad = f16_rn(loss_scale * (2.0f * d / pse) / n_total);
+			grad = loss_grad_store<G>(loss_scale * (2.0f * d / pse) / n_total);
 		}
 	} else if (type == LOSS_L1) {  // l1.h:66-74
 		if constexpr (PDF) {
 			value = fabsf(d) / pdf / n_total;
-			grad = f16_rn(loss_scale * copysignf(1.0f / pdf, d) / n_total);
+			grad = loss_grad_store<G>(loss_scale * copysignf(1.0f / pdf, d) / n_total);
 		} else {
 			value = fabsf(d) / n_total;
-			grad = f16_rn(loss_scale * copysignf(1.0f, d) / n_total);
+			grad = loss_grad_store<G>(loss_scale * copysignf(1.0f, d) / n_total);
 		}
 	} else if (type <= LOSS_SMAPE) {  // relative_l1.h:66-76, mape.h:66-77, smape.h:66-77
 		const float den = type == LOSS_RELATIVE_L1 ? fabsf(p) + 1e-2f
@@ -80,19 +89,19 @@ __device__ __forceinline__ void loss_eval(uint32_t type_rt, float p, float t, fl
 		float scale = 1.0f / den;
 		if constexpr (PDF) scale = scale / pdf;
 		value = fabsf(d) * scale / n_total;
-		grad = f16_rn(loss_scale * copysignf(scale, d) / n_total);  // d == 0: +scale, as copysignf gives
+		grad = loss_grad_store<G>(loss_scale * copysignf(scale, d) / n_total);  // d == 0: +scale, as copysignf gives
 	} else if (type == LOSS_CROSS_ENTROPY) {  // cross_entropy.h:66-76: 1 / n_total is inside factor
 		float factor = -t;
 		if constexpr (PDF) factor = factor / pdf;
 		factor = factor / n_total;
 		value = factor * logf(p);
-		grad = f16_rn(loss_scale * (factor / p));
+		grad = loss_grad_store<G>(loss_scale * (factor / p));
 	} else {  // variance_is.h:66-76: the pdf divides twice
 		float factor = t * t;
 		if constexpr (PDF) factor = factor / pdf;
 		factor = factor / n_total;
 		value = PDF ? factor / p - factor / pdf : factor / p - factor;
-		grad = f16_rn(loss_scale * (-factor / (p * p)));
+		grad = loss_grad_store<G>(loss_scale * (-factor / (p * p)));
 	}
 }
 

@@ -1,10 +1,11 @@
 // optimizers.hip -- the elementwise optimizers beside Adam (reference optimizers/sgd.h, ema.h,
-// lookahead.h, batched.h) as streaming passes over the parameter vector; the arithmetic is in
-// optim_device.h. Every kernel: 256 threads, 8 consecutive parameters per thread (one 16-byte access
+// lookahead.h, batched.h) and the torch optimizer's Adam on a caller's tensors (k_adam_torch) as
+// streaming passes over the parameter vector; the arithmetic is in optim_device.h and adam_device.h. Every kernel: 256 threads, 8 consecutive parameters per thread (one 16-byte access
 // per fp16 array, two per fp32 array), so a workgroup spans OPT_SPAN = 2048 parameters; the last
 // thread with work finishes a count that is no multiple of 8 one parameter at a time. fp32
 // arithmetic, no LDS, no atomics, nothing that depends on the batch. Buffers are whole allocations
 // (16-byte aligned).
+#include "adam_device.h"
 #include "optim_device.h"
 #include "optimizers.h"
 
@@ -146,6 +147,50 @@ __global__ __launch_bounds__(256) void k_pool_cast(const float* __restrict__ poo
 	}
 }
 
+// Adam of the torch optimizer (tinycudann.optim.Adam) on one parameter tensor: adam_tail on the
+// caller's gradient as it is (G = float or _Float16; no loss scale, no fp16 rounding), fp32 masters
+// only. a.n parameters, the first a.n_matrix of them matrix parameters (the boundary may fall inside
+// a thread's 8). The five loads of a thread are independent; a thread none of whose parameters is
+// updated (frozen class, untouched grid entries) stores nothing, else its skipped parameters are
+// rewritten with their unchanged values.
+template <typename G>
+__global__ __launch_bounds__(256) void k_adam_torch(const AdamArgs a, float* __restrict__ w32, const G* __restrict__ grad,
+                                                     float* __restrict__ m1, float* __restrict__ m2, uint32_t* __restrict__ steps) {
+	const size_t n = a.n;
+	OPT_RANGE
+	if (full) {
+		F8 w = load_f8(w32 + i0), v1 = load_f8(m1 + i0), v2 = load_f8(m2 + i0), g;
+		const uint4 sa = *(const uint4*)(steps + i0), sb = *(const uint4*)(steps + i0 + 4);
+		uint32_t st[8] = {sa.x, sa.y, sa.z, sa.w, sb.x, sb.y, sb.z, sb.w};
+		if constexpr (sizeof(G) == 4) {
+			g = load_f8((const float*)grad + i0);
+		} else {
+			const h8 gh = *(const h8*)((const _Float16*)grad + i0);
+#pragma unroll
+			for (int r = 0; r < 8; ++r) g.v[r] = (float)gh[r];
+		}
+		bool any = false;
+#pragma unroll
+		for (int r = 0; r < 8; ++r) any = adam_tail(a, (uint32_t)i0 + r, g.v[r], w.v[r], v1.v[r], v2.v[r], st[r]) || any;
+		if (!any) return;
+		store_f8(w32 + i0, w);
+		store_f8(m1 + i0, v1);
+		store_f8(m2 + i0, v2);
+		*(uint4*)(steps + i0) = make_uint4(st[0], st[1], st[2], st[3]);
+		*(uint4*)(steps + i0 + 4) = make_uint4(st[4], st[5], st[6], st[7]);
+	} else {
+		for (size_t i = i0; i < n; ++i) {
+			float w = w32[i], v1 = m1[i], v2 = m2[i];
+			uint32_t st = steps[i];
+			if (!adam_tail(a, (uint32_t)i, (float)grad[i], w, v1, v2, st)) continue;
+			w32[i] = w;
+			m1[i] = v1;
+			m2[i] = v2;
+			steps[i] = st;
+		}
+	}
+}
+
 #undef OPT_RANGE
 
 inline dim3 opt_grid(size_t n) { return dim3(div_round_up(n, OPT_SPAN)); }
@@ -187,6 +232,15 @@ void launch_batched_pool(hipStream_t st, const void* g16, float* pool, uint32_t 
 	if (!n) return;
 	hipLaunchKernelGGL(k_batched_pool, opt_grid(n), dim3(OPT_THREADS), 0, st, (const _Float16*)g16, pool, (float)multiplier, first ? 1 : 0,
 	                   n);
+	TCNN_HIP_CHECK(hipGetLastError());
+}
+
+void launch_adam_torch(hipStream_t st, const AdamArgs& a, float* w32, const void* grad, bool grad_f16, float* m1, float* m2, uint32_t* steps) {
+	if (!a.n) return;
+	if (grad_f16)
+		hipLaunchKernelGGL(k_adam_torch<_Float16>, opt_grid(a.n), dim3(OPT_THREADS), 0, st, a, w32, (const _Float16*)grad, m1, m2, steps);
+	else
+		hipLaunchKernelGGL(k_adam_torch<float>, opt_grid(a.n), dim3(OPT_THREADS), 0, st, a, w32, (const float*)grad, m1, m2, steps);
 	TCNN_HIP_CHECK(hipGetLastError());
 }
 

@@ -1,4 +1,5 @@
-// torch_ext.cpp -- the torch autograd node of tinycudann.Module in C++ (r06):
+// torch_ext.cpp -- the torch autograd node of tinycudann.Module in C++ (r06), and below it
+// the node of tinycudann.Loss and tinycudann.optim.Adam's step:
 // the reference's `_module_function` / `_module_function_backward` (bindings/torch/tinycudann/
 // modules.py:91-192, over bindings.cpp:79-171) as torch::autograd::Function subclasses calling the same
 // C-ABI entry points (include/tcnn_mi355x.h) the Python front-end calls through ctypes. One pybind call
@@ -163,6 +164,80 @@ struct ModuleFunction : public torch::autograd::Function<ModuleFunction> {
 	}
 };
 
+// ---- tinycudann.Loss: the engine's losses as an autograd node (tcnn_loss_forward / tcnn_loss_backward). The
+// Python twin is tinycudann.loss._loss_function; tinycudann.Loss has checked and converted the arguments:
+// pred [n, dims] fp16 / fp32 with unit column stride, target and pdf (no elements: none) fp32 contiguous. ----
+const float* pdf_ptr(const torch::Tensor& pdf) { return pdf.numel() ? (const float*)pdf.data_ptr() : nullptr; }
+
+torch::Tensor loss_grad(int64_t type, const torch::Tensor& grad_output, const torch::Tensor& pred, const torch::Tensor& target,
+                        const torch::Tensor& pdf) {
+	torch::Tensor go = grad_output;
+	if (go.scalar_type() != torch::kFloat || go.device() != pred.device()) go = go.to(pred.options().dtype(torch::kFloat));
+	torch::Tensor g = torch::empty({pred.size(0), pred.size(1)}, pred.options());
+	check(tcnn_loss_backward((int)type, stream_of(pred), (uint64_t)pred.size(0), (uint32_t)pred.size(1), ptr(pred),
+	                         pred.scalar_type() == torch::kFloat, (uint64_t)pred.stride(0), (const float*)ptr(target), pdf_ptr(pdf),
+	                         (const float*)ptr(go), ptr(g)));
+	return g;
+}
+
+// the gradient as a node of its own, taken only when the backward is recorded (create_graph=True): its
+// backward, the loss's second derivative, is out of scope and says so
+struct LossBackward : public torch::autograd::Function<LossBackward> {
+	static torch::Tensor forward(torch::autograd::AutogradContext* ctx, int64_t type, torch::Tensor grad_output, torch::Tensor pred,
+	                             torch::Tensor target, torch::Tensor pdf) {
+		return loss_grad(type, grad_output, pred, target, pdf);
+	}
+	static torch::autograd::variable_list backward(torch::autograd::AutogradContext* ctx, torch::autograd::variable_list grads) {
+		TORCH_CHECK(false, "tinycudann.Loss: the double backward of a loss is not implemented");
+		return {};
+	}
+};
+
+struct LossFunction : public torch::autograd::Function<LossFunction> {
+	static torch::Tensor forward(torch::autograd::AutogradContext* ctx, int64_t type, torch::Tensor pred, torch::Tensor target, torch::Tensor pdf) {
+		ctx->set_materialize_grads(false);
+		const uint64_t n = (uint64_t)pred.size(0);
+		const uint32_t dims = (uint32_t)pred.size(1);
+		const uint32_t nws = tcnn_loss_workspace_floats(n, dims);
+		const auto f32 = pred.options().dtype(torch::kFloat);
+		torch::Tensor value = torch::empty({}, f32), ws = torch::empty({(int64_t)nws}, f32);
+		check(tcnn_loss_forward((int)type, stream_of(pred), n, dims, ptr(pred), pred.scalar_type() == torch::kFloat, (uint64_t)pred.stride(0),
+		                        (const float*)ptr(target), pdf_ptr(pdf), (float*)ptr(ws), nws, (float*)ptr(value)));
+		ctx->saved_data["type"] = type;
+		ctx->save_for_backward({pred, target, pdf});
+		return value;
+	}
+
+	static torch::autograd::variable_list backward(torch::autograd::AutogradContext* ctx, torch::autograd::variable_list grads) {
+		torch::autograd::variable_list out(4);  // type, pred, target, pdf: only pred has a gradient
+		if (!grads[0].defined() || !ctx->needs_input_grad(0)) return out;
+		const auto saved = ctx->get_saved_variables();
+		const torch::Tensor pdf = saved[2];
+		const int64_t type = ctx->saved_data.at("type").toInt();
+		out[1] = torch::GradMode::is_enabled() ? LossBackward::apply(type, grads[0], saved[0], saved[1], pdf)
+		                                       : loss_grad(type, grads[0], saved[0], saved[1], pdf);
+		return out;
+	}
+};
+
+torch::Tensor loss_apply(int64_t type, torch::Tensor pred, torch::Tensor target, c10::optional<torch::Tensor> pdf) {
+	// an absent data_pdf travels through the graph as a tensor without elements (an undefined one has no device)
+	return LossFunction::apply(type, pred, target, pdf.has_value() ? *pdf : torch::empty({0}, target.options()));
+}
+
+// ---- tinycudann.optim.Adam: one step on one parameter tensor (tcnn_adam_step_buffers). hyper: the twelve
+// options in tcnn_adam_options order; table: the bias-correction factors (undefined: none) ----
+void adam_step(torch::Tensor param, torch::Tensor grad, torch::Tensor m1, torch::Tensor m2, torch::Tensor steps, c10::optional<torch::Tensor> table,
+               int64_t n_matrix, int64_t step, std::vector<double> hyper) {
+	TORCH_CHECK(hyper.size() == 12, "tinycudann.optim.Adam: twelve hyper-parameters expected");
+	const tcnn_adam_options o{(float)hyper[0], (float)hyper[1], (float)hyper[2],  (float)hyper[3], (float)hyper[4], (float)hyper[5],
+	                          (float)hyper[6], (float)hyper[7], (float)hyper[8], (int)hyper[9],   (int)hyper[10],  (int)hyper[11]};
+	const bool has = table.has_value() && table->defined();
+	check(tcnn_adam_step_buffers(stream_of(param), &o, (uint64_t)param.numel(), (uint64_t)n_matrix, (uint32_t)step, (float*)ptr(param), ptr(grad),
+	                             grad.scalar_type() == torch::kHalf, (float*)ptr(m1), (float*)ptr(m2), (uint32_t*)ptr(steps),
+	                             has ? (const float*)table->data_ptr() : nullptr, has ? (uint32_t)table->numel() : 0u));
+}
+
 // owner: the Python object whose collection destroys `module` (called with the GIL held, as every pybind function)
 torch::Tensor module_apply(int64_t module, py::object owner, torch::Tensor input, torch::Tensor params, double loss_scale) {
 	return ModuleFunction::apply(module, c10::IValue(c10::ivalue::ConcretePyObjectHolder::create(std::move(owner))), input, params, loss_scale);
@@ -174,5 +249,8 @@ TORCH_LIBRARY(tcnn_mi355x, m) { m.class_<NativeCtx>("NativeCtx"); }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
 	m.doc() = "tinycudann (MI355X) torch autograd node in C++ over the engine's C-ABI";
+	m.def("loss_apply", &loss_apply, "tinycudann.Loss forward with its C++ autograd node (loss type, prediction, target, data_pdf or None)");
+	m.def("adam_step", &adam_step,
+	      "tinycudann.optim.Adam on one parameter tensor (param, grad, m1, m2, steps, bias-factor table or None, n_matrix, step, 12 hyper-parameters)");
 	m.def("module_apply", &module_apply, "tinycudann.Module forward with its C++ autograd node (handle, its owner, input, params, loss_scale)");
 }

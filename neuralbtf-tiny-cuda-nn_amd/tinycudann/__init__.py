@@ -5,6 +5,8 @@ The compute path is the HIP library lib/libtcnn_mi355x.so driven through its C-A
 (include/tcnn_mi355x.h); PyTorch only provides device memory and the stream.
 """
 from tinycudann._lib import TcnnError  # noqa: F401
+from tinycudann import optim  # noqa: F401
+from tinycudann.loss import Loss  # noqa: F401
 from tinycudann.trainer import Trainer, create_from_config  # noqa: F401
 
 try:

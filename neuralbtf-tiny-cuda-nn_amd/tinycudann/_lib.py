@@ -49,6 +49,7 @@ _SIGS = {
     "tcnn_module_n_input_dims": (c_uint32, [c_void_p]),
     "tcnn_module_n_output_dims": (c_uint32, [c_void_p]),
     "tcnn_module_n_params": (c_uint64, [c_void_p]),
+    "tcnn_module_n_network_params": (c_uint64, [c_void_p]),
     "tcnn_module_param_precision": (c_int, [c_void_p]),
     "tcnn_module_output_precision": (c_int, [c_void_p]),
     "tcnn_module_initialize_params": (c_int, [c_void_p, c_uint64, c_void_p, c_float]),
@@ -78,6 +79,14 @@ _SIGS = {
     "tcnn_trainer_loss_value": (c_int, [c_void_p, c_void_p, c_void_p]),
     "tcnn_loss_evaluate": (c_int, [c_char_p, c_void_p, c_uint32, c_uint32, c_uint32, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p]),
+    "tcnn_loss_type": (c_int, [c_char_p]),
+    "tcnn_loss_workspace_floats": (c_uint32, [c_uint64, c_uint32]),
+    "tcnn_loss_forward": (c_int, [c_int, c_void_p, c_uint64, c_uint32, c_void_p, c_int, c_uint64, c_void_p, c_void_p, c_void_p, c_uint32,
+                                  c_void_p]),
+    "tcnn_loss_backward": (c_int, [c_int, c_void_p, c_uint64, c_uint32, c_void_p, c_int, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "tcnn_adam_step_buffers": (c_int, [c_void_p, c_void_p, c_uint64, c_uint64, c_uint32, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_uint32]),
+    "tcnn_adam_bias_factors": (c_int, [c_float, c_float, c_uint32, c_uint32, c_void_p]),
     "tcnn_trainer_loss_device": (c_void_p, [c_void_p]),
     "tcnn_trainer_inference": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p]),
     "tcnn_trainer_n_params": (c_uint64, [c_void_p]),
@@ -133,6 +142,13 @@ _DEBUG_SIGS = {
     "tcnn_debug_hfma": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32]),
     "tcnn_debug_peer_loopback": (c_int, [c_void_p, c_int]),
 }
+
+
+class AdamOptions(ctypes.Structure):
+    """tcnn_adam_options (include/tcnn_mi355x.h)"""
+    _fields_ = [(n, c_float) for n in (
+        "learning_rate", "beta1", "beta2", "epsilon", "l2_reg", "relative_decay", "absolute_decay", "clipping_magnitude",
+        "non_matrix_learning_rate_factor")] + [(n, c_int) for n in ("adabound", "optimize_matrix_params", "optimize_non_matrix_params")]
 
 
 class TcnnError(RuntimeError):
