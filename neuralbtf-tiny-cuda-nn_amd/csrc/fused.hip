@@ -124,7 +124,7 @@ void launch_fused_train(hipStream_t st, const GridCall& g, uint32_t W, uint32_t 
                         uint32_t B, uint32_t dims, float loss_scale, const void* params16, const void* table16,
                         const float* pos, const float* target, void* out16, void* dLdenc_pairs,
                         float* wgrad_partial, float* loss_partial, uint32_t n_blocks, const void* dout16, const void* wimage,
-                        uint32_t loss_type, const void* enc16, float dout_scale, float* dy_bound) {
+                        uint32_t loss_type, const void* enc16, float dout_scale, float* dy_bound, uint32_t wt_stores) {
 	const uint32_t D = g.D;
 	const HashType h = g.hash;
 	TCNN_CHECK(B % 32 == 0, "fused train: batch must be a multiple of 32");
@@ -154,6 +154,7 @@ void launch_fused_train(hipStream_t st, const GridCall& g, uint32_t W, uint32_t 
 	a.prof = nullptr;
 	TCNN_CHECK(!dy_bound || (!dout16 && !enc16), "fused train: slice sums only with the loss inside and the encoding gathered");
 	a.dy_bound = dy_bound;
+	a.wt_stores = wt_stores;
 	if (!dout16 && loss_type > LOSS_L2) {
 		// the seven other losses: one kernel symbol per loss (k_fused_train_grid_loss, fused_loss_*.hip), the
 		// loss inside and the encoding gathered

@@ -554,7 +554,7 @@ extern template void grid_bwd_d<4>(hipStream_t, uint32_t, HashType, const GridBw
 void launch_grid_bwd(hipStream_t st, const GridCall& gc, uint32_t B, const float* pos, uint32_t pos_stride, const void* dLdy16,
                      int dy_layout, uint32_t dy_stride, const GridSlice* slices, uint32_t n_slices, uint32_t n_chunks, float* partial,
                      uint32_t partial_stride, const GridBwdEpilogue* ep, const GridSlice* host_slices, const LevelInfo* host_levels,
-                     const float* dy_bound) {
+                     const float* dy_bound, uint32_t wt_stores) {
 	const uint32_t n_tail = (ep && ep->enabled) ? ep->n_mlp_groups : 0u;
 	if (n_tail == 0 && (n_slices == 0 || B == 0)) return;  // callers zero the gradient of empty batches
 	if (B == 0) n_slices = 0;
@@ -581,6 +581,7 @@ void launch_grid_bwd(hipStream_t st, const GridCall& gc, uint32_t B, const float
 	gl.opts = gc.opts;
 	gl.dy_bound = dy_layout == 0 ? dy_bound : nullptr;
 	gl.fallback_count = nullptr;
+	gl.wt_stores = wt_stores;
 	if (g_count_fallbacks) {
 		gl.fallback_count = (uint32_t*)g_fallbacks.get(4);
 		TCNN_HIP_CHECK(hipMemsetAsync(gl.fallback_count, 0, 4, st));

@@ -14,6 +14,7 @@
 #include "grid_bwd_scale.h"
 #include "grid_device.h"
 #include "grid_dispatch.h"
+#include "wt_store.h"
 
 namespace tcnn_amd {
 
@@ -441,7 +442,7 @@ __global__ __launch_bounds__(GRID_BWD_THREADS) void k_grid_bwd_lds(
 	const GridSlice* __restrict__ items, float* __restrict__ partial, uint32_t partial_stride,
 	const LevelInfo* __restrict__ levels, uint32_t hash_grid, uint32_t interp_u, uint32_t pts_per_chunk, uint32_t n_items,
 	uint32_t n_chunks, const GridBwdEpilogue ep, unsigned long long* dbg_times, const GridOpts o, const GridBwdTables tb,
-	const float* __restrict__ dy_bound, uint32_t* fallback_count) {
+	const float* __restrict__ dy_bound, uint32_t* fallback_count, uint32_t wt_stores) {
 	extern __shared__ __attribute__((aligned(16))) int acc[];
 	const unsigned long long t_start = dbg_times ? wall_clock64() : 0ull;
 	__shared__ float red[GRID_BWD_THREADS / 64];
@@ -684,6 +685,9 @@ __global__ __launch_bounds__(GRID_BWD_THREADS) void k_grid_bwd_lds(
 	// write the chunk slab (GridSlabMap layout: this item's accumulators are one contiguous range)
 	const float inv = finite ? ldexpf(1.0f, -e) : __builtin_nanf("");
 	float* dst = partial + (size_t)chunk * partial_stride + (size_t)li.offset * F + (size_t)f0 * li.size + (size_t)it.begin * nf;
+	// write-through (wt_store.h): the slab is read by the next launch only (k_adam, or the sequential reductions);
+	// the 16-byte stores go through a buffer resource over this workgroup's own range (wave-uniform base, small offsets)
+	const bool wt = (wt_stores & WT_GRID_SLAB) != 0;
 	if (mode == 0) {  // decode the packed int32 pairs, two entries per thread (16-byte stores)
 		const long long* a64 = (const long long*)acc;
 		auto dec = [&](long long t) {
@@ -692,25 +696,51 @@ __global__ __launch_bounds__(GRID_BWD_THREADS) void k_grid_bwd_lds(
 			return make_float2((float)lo * inv, (float)hi * inv);
 		};
 		const bool al = (((uintptr_t)dst) & 15) == 0;
-		for (uint32_t j = 2 * threadIdx.x; j < len; j += 2 * blockDim.x) {
-			const float2 a = dec(a64[j]);
-			if (al && j + 1 < len) {
-				const float2 b = dec(a64[j + 1]);
-				*(f4*)(dst + 2 * j) = f4{a.x, a.y, b.x, b.y};
-			} else {
-				*(float2*)(dst + 2 * j) = a;
-				if (j + 1 < len) *(float2*)(dst + 2 * j + 2) = dec(a64[j + 1]);
+		if (wt) {
+			const wt_rsrc rs = wt_make_rsrc(dst, 2 * len * 4);
+			for (uint32_t j = 2 * threadIdx.x; j < len; j += 2 * blockDim.x) {
+				const float2 a = dec(a64[j]);
+				if (al && j + 1 < len) {
+					const float2 b = dec(a64[j + 1]);
+					wt_store16(rs, 8 * j, f4{a.x, a.y, b.x, b.y});
+				} else {
+					wt_store((float2*)(dst + 2 * j), a);
+					if (j + 1 < len) wt_store((float2*)(dst + 2 * j + 2), dec(a64[j + 1]));
+				}
+			}
+		} else {
+			for (uint32_t j = 2 * threadIdx.x; j < len; j += 2 * blockDim.x) {
+				const float2 a = dec(a64[j]);
+				if (al && j + 1 < len) {
+					const float2 b = dec(a64[j + 1]);
+					*(f4*)(dst + 2 * j) = f4{a.x, a.y, b.x, b.y};
+				} else {
+					*(float2*)(dst + 2 * j) = a;
+					if (j + 1 < len) *(float2*)(dst + 2 * j + 2) = dec(a64[j + 1]);
+				}
 			}
 		}
 	} else {
 		const uint32_t n = len * nf;
 		const bool al = (((uintptr_t)dst) & 15) == 0;
-		for (uint32_t j = 4 * threadIdx.x; j < n; j += 4 * blockDim.x) {
-			if (al && j + 4 <= n) {
-				const int4 v = *(const int4*)(acc + j);
-				*(f4*)(dst + j) = f4{(float)v.x * inv, (float)v.y * inv, (float)v.z * inv, (float)v.w * inv};
-			} else {
-				for (uint32_t k = j; k < n && k < j + 4; ++k) dst[k] = (float)acc[k] * inv;
+		if (wt) {
+			const wt_rsrc rs = wt_make_rsrc(dst, n * 4);
+			for (uint32_t j = 4 * threadIdx.x; j < n; j += 4 * blockDim.x) {
+				if (al && j + 4 <= n) {
+					const int4 v = *(const int4*)(acc + j);
+					wt_store16(rs, 4 * j, f4{(float)v.x * inv, (float)v.y * inv, (float)v.z * inv, (float)v.w * inv});
+				} else {
+					for (uint32_t k = j; k < n && k < j + 4; ++k) wt_store(dst + k, (float)acc[k] * inv);
+				}
+			}
+		} else {
+			for (uint32_t j = 4 * threadIdx.x; j < n; j += 4 * blockDim.x) {
+				if (al && j + 4 <= n) {
+					const int4 v = *(const int4*)(acc + j);
+					*(f4*)(dst + j) = f4{(float)v.x * inv, (float)v.y * inv, (float)v.z * inv, (float)v.w * inv};
+				} else {
+					for (uint32_t k = j; k < n && k < j + 4; ++k) dst[k] = (float)acc[k] * inv;
+				}
 			}
 		}
 	}
@@ -742,6 +772,7 @@ struct GridBwdLaunch {
 	GridBwdTables tb;
 	const float* dy_bound;     // the fused kernel's slice sums of max_f |dL/dy| (null: every workgroup takes the exact pre-pass)
 	uint32_t* fallback_count;  // debug: workgroups that had dy_bound but took the exact pre-pass (null: not counted)
+	uint32_t wt_stores;        // WT_GRID_SLAB (wt_store.h): the chunk slabs are written through L2
 };
 
 template <uint32_t D, uint32_t F, HashType H>
@@ -753,7 +784,7 @@ static void grid_bwd_t(hipStream_t st, const GridBwdLaunch& gl) {
 	const auto kernel = gl.opts.active ? k_grid_bwd_lds<D, F, H, true> : k_grid_bwd_lds<D, F, H, false>;
 	hipLaunchKernelGGL(kernel, dim3(gl.n_workgroups), dim3(GRID_BWD_THREADS), GRID_BWD_LDS_BYTES, st, gl.layout, gl.B, gl.pos, gl.pos_stride,
 	                   gl.dLdy, gl.dy_stride, gl.items, gl.partial, gl.partial_stride, gl.levels, gl.hash_grid, gl.interp, gl.pts_per_chunk,
-	                   gl.n_items, gl.n_chunks, gl.ep, gl.dbg_times, gl.opts, gl.tb, gl.dy_bound, gl.fallback_count);
+	                   gl.n_items, gl.n_chunks, gl.ep, gl.dbg_times, gl.opts, gl.tb, gl.dy_bound, gl.fallback_count, gl.wt_stores);
 }
 
 // every (F, hash) instantiation of one D: instantiated in grid_bwd_d{2,3,4}.hip only

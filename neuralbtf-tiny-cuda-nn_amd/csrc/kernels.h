@@ -164,7 +164,8 @@ void launch_fused_train(hipStream_t st, const GridCall& g, uint32_t W, uint32_t 
                         uint32_t loss_type = 0,
                         const void* enc16 = nullptr,  // enc16: the encoding read from memory, SoA [IN][B] (no gathers)
                         float dout_scale = 1.0f,      // dout16 is used as fp16(dout16 * dout_scale)
-                        float* dy_bound = nullptr);   // [L][B/32] slice sums of max_f |dL/denc| (grid_bwd_lds.h); null: none
+                        float* dy_bound = nullptr,    // [L][B/32] slice sums of max_f |dL/denc| (grid_bwd_lds.h); null: none
+                        uint32_t wt_stores = 0);      // WT_WGRAD_SLAB (wt_store.h): the slabs are written through L2
 // LDS weight image of the fused kernels, built once per parameter update.
 size_t fused_weight_image_bytes(uint32_t W, uint32_t IN, uint32_t NH);
 void launch_pack_weights(hipStream_t st, uint32_t W, uint32_t IN, uint32_t NH, const void* params16, void* image);
@@ -196,7 +197,8 @@ void launch_grid_bwd(hipStream_t st, const GridCall& g, uint32_t B, const float*
                      const LevelInfo* host_levels = nullptr,
                      // dy_bound (layout 0 only): [L][B/32] slice sums of max_f |dL/dy| written by the fused kernel that
                      // wrote dLdy16 (launch_fused_train) -- the streaming pre-pass of grid_bwd_lds.h; null: the exact one
-                     const float* dy_bound = nullptr);
+                     const float* dy_bound = nullptr,
+                     uint32_t wt_stores = 0);  // WT_GRID_SLAB (wt_store.h): the chunk slabs are written through L2
 // Debug (debug_api.h): count the workgroups of every following launch_grid_bwd that were given
 // dy_bound but took the exact pre-pass; the count of the last launch (synchronises the device).
 void grid_bwd_debug_count_fallbacks(bool on);

@@ -26,6 +26,7 @@
 #include "lds_dma.h"
 #include "kernels.h"
 #include "loss_device.h"
+#include "wt_store.h"
 
 namespace tcnn_amd {
 
@@ -351,6 +352,7 @@ struct FusedTrainArgs {
 	// optional [L][B/32]: per (level, 32-sample slice) the fp32 sum of max_f |dL/denc| as stored -- the
 	// grid backward's fixed-point range without its pass over dLdenc (grid_bwd_lds.h); null: not emitted
 	float* dy_bound;
+	uint32_t wt_stores;     // WT_WGRAD_SLAB (wt_store.h): the slab store writes through L2 (wave-uniform)
 };
 
 // max(|lo|, |hi|) of a stored fp16 pair as fp32, +inf if either is not finite (the grid backward's
@@ -709,6 +711,7 @@ __device__ __forceinline__ void block_reduce_wgrad(WgradAcc<W, IN, NH>& acc, flo
 		for (int nt = 0; nt < NT; ++nt) io(acc.Wo[nt]);
 	};
 	float* dst = a.wgrad_partial + (size_t)blockIdx.x * N;
+	const bool wt = (a.wt_stores & WT_WGRAD_SLAB) != 0;  // the slab is read by the next launch only
 	if constexpr (WAVES == 4) {
 		// (w0 + w2) + (w1 + w3): waves 2, 3 write, waves 0, 1 add and write their sums back in place
 		// (each lane rewrites only the f4s it read), then all four waves add the two sums and store the
@@ -730,7 +733,10 @@ __device__ __forceinline__ void block_reduce_wgrad(WgradAcc<W, IN, NH>& acc, flo
 			if ((N / 4) % (WAVES * 64) != 0 && g >= N / 4) break;
 			const f4 v = ((const f4*)slab)[g] + ((const f4*)(slab + N))[g];
 #pragma unroll
-			for (int r = 0; r < 4; ++r) dst[wgrad_frag_to_param<W, IN, NH>((uint32_t)(4 * g + r))] = v[r];
+			for (int r = 0; r < 4; ++r) {
+				float* const p = dst + wgrad_frag_to_param<W, IN, NH>((uint32_t)(4 * g + r));
+				if (wt) wt_store(p, v[r]); else *p = v[r];
+			}
 		}
 		pstamp();
 	} else {
@@ -748,7 +754,10 @@ __device__ __forceinline__ void block_reduce_wgrad(WgradAcc<W, IN, NH>& acc, flo
 		if (wave == 0) visit(slab, false);
 		__syncthreads();
 		pstamp();
-		for (int f = tid; f < N; f += WAVES * 64) dst[wgrad_frag_to_param<W, IN, NH>((uint32_t)f)] = slab[f];
+		for (int f = tid; f < N; f += WAVES * 64) {
+			float* const p = dst + wgrad_frag_to_param<W, IN, NH>((uint32_t)f);
+			if (wt) wt_store(p, slab[f]); else *p = slab[f];
+		}
 		pstamp();
 	}
 	if (tid == 0) {

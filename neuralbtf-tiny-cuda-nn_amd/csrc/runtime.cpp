@@ -109,6 +109,7 @@ EngineSwitches EngineSwitches::from_env() {
 	if (const char* e = std::getenv("TCNN_GRID_BWD_RANGES"))
 		if (std::atoi(e) > 0) s.grid_bwd_ranges = (uint32_t)std::atoi(e);
 	if (const char* e = std::getenv("TCNN_GRID_BWD_STREAM")) s.no_grid_bwd_stream = std::string(e) == "0";
+	if (const char* e = std::getenv("TCNN_WT_STORES")) s.wt_stores = (uint32_t)std::strtoul(e, nullptr, 0) & WT_STORES_ALL;
 	if (const char* e = std::getenv("TCNN_GRID_BWD_PLAN")) s.grid_bwd_plan = std::string(e) == "feature" ? 1 : (std::string(e) == "range" ? 0 : -1);
 	return s;
 }
@@ -364,7 +365,7 @@ void GridEncodingHost::backward_items(hipStream_t st, GridBwdBufs& w, uint32_t B
 	const GridPlan& pl = plans[w.plan];
 	if (!pl.slices.empty()) w.partial.reserve((size_t)n_chunks * n_lds_params * 4);
 	launch_grid_bwd(st, call(), B, pos, pstride, dy, layout, dy_stride, pl.d_slices.as<GridSlice>(), (uint32_t)pl.slices.size(), n_chunks,
-	                w.partial.as<float>(), n_lds_params, ep, pl.slices.data(), levels.data(), dy_bound);
+	                w.partial.as<float>(), n_lds_params, ep, pl.slices.data(), levels.data(), dy_bound, sw.wt_stores);
 }
 
 void GridEncodingHost::backward_bin(hipStream_t st, GridBwdBufs& w, uint32_t B, const float* pos, uint32_t pstride, const void* dy,
@@ -1036,7 +1037,7 @@ void NetworkHost::fused_kernel(hipStream_t st, StepWorkspace& ws, uint32_t B, co
 	launch_fused_train(st, grid->call(), mlp.width, mlp.n_input, mlp.n_hidden_layers, mlp.activation, B, dims, loss_scale, params16,
 	                   enc_params(params16), pos, target, out16, ws.dLdenc.p, ws.wgrad_partial.as<float>(), ws.loss_partial.as<float>(), nb,
 	                   dout16, use_image ? ws.wimage.p : nullptr, loss_type, enc_soa, dout16 ? ext_dout_scale : 1.0f,
-	                   ws.dy_bound_live ? ws.dy_bound.as<float>() : nullptr);
+	                   ws.dy_bound_live ? ws.dy_bound.as<float>() : nullptr, sw.wt_stores);
 }
 
 void NetworkHost::grid_backward(hipStream_t st, StepWorkspace& ws, uint32_t B, const float* pos, GridBwdEpilogue* ep) {

@@ -16,6 +16,7 @@
 #include "grid_device.h"
 #include "kernels.h"
 #include "optimizer_tree.h"
+#include "wt_store.h"
 
 namespace tcnn_amd {
 
@@ -88,6 +89,9 @@ struct EngineSwitches {
 	uint32_t grid_bwd_ranges = 0;   // TCNN_GRID_BWD_RANGES: at least this many entry ranges per hashed level (tuning)
 	int grid_bwd_plan = -1;         // TCNN_GRID_BWD_PLAN=range|feature: force one work plan (A/B; -1: by batch)
 	bool no_grid_bwd_stream = false;  // TCNN_GRID_BWD_STREAM=0: no dy_bound from the fused kernel, exact pre-pass everywhere (A/B)
+	// TCNN_WT_STORES=<mask>: the training step's hand-off stores that write through L2 (wt_store.h:
+	// WT_WGRAD_SLAB 1, WT_GRID_SLAB 2); 0: all plain (A/B). Results do not depend on it.
+	uint32_t wt_stores = WT_STORES_DEFAULT;
 	static EngineSwitches from_env();
 };
 
