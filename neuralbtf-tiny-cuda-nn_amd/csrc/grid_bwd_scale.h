@@ -21,13 +21,15 @@ TCNN_SCALE_HD float grid_bwd_scale_lim(float m, float P, uint32_t D) {
 	return (2147483647.0f - (float)(1u << D) * P) / (m * 1.01f);
 }
 
-// e = floor(log2(lim)), clamped; 0 for an empty or non-finite sum (the caller turns a non-finite
-// sum into a NaN gradient).
-TCNN_SCALE_HD int grid_bwd_scale_exp(float m, float P, uint32_t D) {
+// e = floor(log2(lim)), clamped to [-126, e_max]; 0 for an empty or non-finite sum (the caller turns a
+// non-finite sum into a NaN gradient). e_max: the precision trait's EXP_MAX (grid_bwd_lds.h); the default
+// is the fp16 kernel's, which fp16 dL/dy never reaches (a non-zero sum is >= 2^-24, so lim < 2^55).
+constexpr int GRID_BWD_EXP_MAX_F16 = 100;
+TCNN_SCALE_HD int grid_bwd_scale_exp(float m, float P, uint32_t D, int e_max = GRID_BWD_EXP_MAX_F16) {
 	int e = 0;
 	if (m > 0.0f && std::isfinite(m)) {
 		e = ilogbf(grid_bwd_scale_lim(m, P, D));
-		e = e < 100 ? e : 100;
+		e = e < e_max ? e : e_max;
 		e = e > -126 ? e : -126;
 	}
 	return e;

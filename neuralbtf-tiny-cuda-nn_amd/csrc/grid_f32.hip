@@ -138,95 +138,35 @@ void launch_grid_fwd_f32(hipStream_t st, const GridCall& gc, uint32_t B, const f
 // 2^e is the item's scale from the chunk's sum of |dL/dy| as in k_grid_bwd_lds. Items always hold all F
 // features (GridEncodingHost::plan_f32), so the slabs are in parameter order.
 
-template <uint32_t F>
-__device__ __forceinline__ void load_dy_f32(const float* __restrict__ dLdy, uint32_t dy_stride, uint32_t level, uint32_t i, bool vec,
-                                            float* dy) {
-	const FVec<F> v = load_fvec<F>(dLdy + (size_t)i * dy_stride + level * F, vec);
+// The fp32 precision trait of the phases in grid_bwd_lds.h (the fields: see PrecF16 there).
+struct PrecF32 {
+	// the fp32 forward multiplies fp32 entries by the unrounded fp32 weight (encode_level_f32)
+	static __device__ __forceinline__ float round_weight(float w) { return w; }
+	static constexpr int EXP_MAX = 126;  // fp32 dL/dy may be tiny: scales up to 2^126 keep its bits
+	// positions and dL/dy of the points in flight stay live across their loads, U (D + F) registers with F
+	// up to 8 fp32 features; 4 is what the fp32 modules were merged with (8 was not measured here)
+	static constexpr uint32_t POINTS_IN_FLIGHT = 4;
+	// the D == 2 fast paths round weights to fp16 and read packed fp16 dL/dy; no fp32 form was written
+	static constexpr bool FAST_2D = false;
+	// the options instantiation (max_level, stochastic interpolation) takes the generic index for every
+	// item: one accumulation body instead of four (which ran it out of scalar registers)
+	static constexpr bool OPTS_ALL_KINDS = false;
+	// with one chunk the slab is the caller's gradient buffer, of which only 4-byte alignment is known
+	static constexpr bool SLAB_PAIR_ALIGNED = false;
+	const float* dLdy;  // AoS rows [B][dy_stride], level l at columns [l F, l F + F)
+	uint32_t dy_stride;
+	bool vec;  // every row's level slice is FVec-aligned
+	template <uint32_t F>
+	__device__ __forceinline__ void load(uint32_t level, uint32_t i, float* dy) const {
+		const FVec<F> v = load_fvec<F>(dLdy + (size_t)i * dy_stride + level * F, vec);
 #pragma unroll
-	for (uint32_t f = 0; f < F; ++f) dy[f] = v.v[f];
-}
-
-// One point's corner updates of one item (accum_point of grid_bwd_lds.h with fp32 weights). dy: the
-// point's dL/dy times the item's scale. PACK (F == 2): both features as one int64 add per corner.
-template <uint32_t D, uint32_t F, HashType H, int KIND, bool PACK, bool OPTS>
-__device__ __forceinline__ void accum_point_f32(const float (&x)[D], const float (&dy)[F], uint32_t i, uint32_t level, uint32_t B,
-                                                const LevelInfo& li, bool hash_grid, Interp interp, uint32_t begin, uint32_t len, int* acc,
-                                                const GridOpts& o) {
-	float p[D];
-	uint32_t pg[D];
-#pragma unroll
-	for (uint32_t d = 0; d < D; ++d) pos_fract(x[d], li.scale, interp, p[d], pg[d]);
-	const bool nearest = interp == Interp::Nearest;
-	// stochastic interpolation (grid.h:284-298): one corner, chosen per (point, level), weight 1
-	const bool single = nearest || (OPTS && o.stochastic);
-	uint32_t cbits = 0;
-	if (single && !nearest) {
-		const float smp = random_val_1337(i + level * B);
-#pragma unroll
-		for (uint32_t d = 0; d < D; ++d) cbits |= (smp >= p[d] ? 0u : 1u) << d;
+		for (uint32_t f = 0; f < F; ++f) dy[f] = v.v[f];
 	}
-#pragma unroll
-	for (uint32_t c0 = 0; c0 < (1u << D); ++c0) {
-		if (single && c0 > 0) break;
-		const uint32_t c = single ? cbits : c0;
-		float w = 1.0f;
-		uint32_t local[D];
-#pragma unroll
-		for (uint32_t d = 0; d < D; ++d) {
-			if ((c & (1u << d)) == 0) { w *= 1.0f - p[d]; local[d] = pg[d]; }
-			else { w *= p[d]; local[d] = pg[d] + 1; }
-		}
-		if (single) w = 1.0f;
-		const uint32_t rel = level_index<D, H, KIND>(hash_grid, li.size, li.res, local) - begin;
-		if constexpr (KIND == IDX_GENERIC || KIND == IDX_HASH_RANGE) {  // entry ranges do not cover the level
-			if (rel >= len) continue;
-		}
-		if constexpr (PACK) {
-			const int a = __float2int_rn(w * dy[0]);
-			const int b = __float2int_rn(w * dy[1]);
-			const unsigned long long pk = (unsigned long long)(((long long)b << 32) + (long long)a);
-			__hip_atomic_fetch_add((unsigned long long*)acc + rel, pk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-		} else {
-#pragma unroll
-			for (uint32_t f = 0; f < F; ++f) lds_add_i32(&acc[rel * F + f], w * dy[f]);
-		}
-	}
-}
+};
 
-template <uint32_t D, uint32_t F, HashType H, int KIND, bool OPTS>
-__device__ __forceinline__ void grid_bwd_points_f32(uint32_t B, const float* __restrict__ pos, uint32_t pstride,
-                                                    const float* __restrict__ dLdy, uint32_t dy_stride, bool vec, uint32_t level,
-                                                    const LevelInfo& li, bool hash_grid, Interp interp, uint32_t begin, uint32_t len,
-                                                    uint32_t i0, uint32_t i1, float scale, int* acc, const GridOpts& o) {
-	constexpr uint32_t U = 4;  // points in flight per thread
-	for (uint32_t base = i0 + threadIdx.x; base < i1; base += U * blockDim.x) {
-		float xs[U][D], dy[U][F];
-#pragma unroll
-		for (uint32_t u = 0; u < U; ++u) {
-			const uint32_t i = base + u * blockDim.x;
-			if (i < i1) {
-#pragma unroll
-				for (uint32_t d = 0; d < D; ++d) xs[u][d] = pos[(size_t)i * pstride + d];
-				load_dy_f32<F>(dLdy, dy_stride, level, i, vec, dy[u]);
-			} else {
-#pragma unroll
-				for (uint32_t d = 0; d < D; ++d) xs[u][d] = 0.0f;
-#pragma unroll
-				for (uint32_t f = 0; f < F; ++f) dy[u][f] = 0.0f;
-			}
-			const bool masked = OPTS && i < i1 && (float)level > grid_max_level(o, i, F) + 1e-3f;  // grid.h:242-244
-#pragma unroll
-			for (uint32_t f = 0; f < F; ++f) dy[u][f] = masked ? 0.0f : dy[u][f] * scale;
-		}
-#pragma unroll
-		for (uint32_t u = 0; u < U; ++u) {
-			if (base + u * blockDim.x >= i1) break;
-			accum_point_f32<D, F, H, KIND, F == 2, OPTS>(xs[u], dy[u], base + u * blockDim.x, level, B, li, hash_grid, interp, begin, len,
-			                                             acc, o);
-		}
-	}
-}
-
+// k_grid_bwd_lds's phases with the fp32 trait: no network tail, no by-value tables, no streaming or
+// register-resident pre-pass (PrecF32::FAST_2D), plain slab stores (write-through, wt_store.h, is the
+// training step's policy; this kernel never had it).
 template <uint32_t D, uint32_t F, HashType H, bool OPTS>
 __global__ __launch_bounds__(GRID_BWD_THREADS) void k_grid_bwd_lds_f32(
 	uint32_t B, const float* __restrict__ pos, uint32_t pstride, const float* __restrict__ dLdy, uint32_t dy_stride, uint32_t vec,
@@ -234,132 +174,38 @@ __global__ __launch_bounds__(GRID_BWD_THREADS) void k_grid_bwd_lds_f32(
 	uint32_t hash_grid, uint32_t interp_u, uint32_t pts_per_chunk, uint32_t n_chunks, const GridOpts o) {
 	extern __shared__ __attribute__((aligned(16))) int acc[];
 	__shared__ float red[GRID_BWD_THREADS / 64];
-	const uint32_t item = blockIdx.x / n_chunks, chunk = blockIdx.x % n_chunks;  // chunk-minor, as k_grid_bwd_lds
+	// 2. item and level load (chunk-minor, as k_grid_bwd_lds). Items hold all F features.
+	const uint32_t item = blockIdx.x / n_chunks, chunk = blockIdx.x % n_chunks;
 	const GridSlice it = items[item];
 	const LevelInfo li = levels[it.level];
 	const uint32_t len = it.end - it.begin;
+	constexpr uint32_t nf = F, f0 = 0;
+	constexpr int MODE = F == 2 ? 0 : 2;
 	const Interp interp = (Interp)interp_u;
 	const uint32_t i0 = chunk * pts_per_chunk;
 	const uint32_t i1 = min(B, i0 + pts_per_chunk);
-	const bool dyvec = vec != 0;
-
-	// replicas of a small item's accumulators (wave w adds into replica w % R), as k_grid_bwd_lds
-	const uint32_t slots = len * F;
-	const uint32_t R = max(1u, min(16u, GRID_BWD_SLOTS / max(slots, 1u)));
-	const uint32_t nz = R * slots;
-	for (uint32_t j = 4 * threadIdx.x; j + 4 <= nz; j += 4 * blockDim.x) *(int4*)(acc + j) = int4{0, 0, 0, 0};
-	for (uint32_t j = nz / 4 * 4 + threadIdx.x; j < nz; j += blockDim.x) acc[j] = 0;
-	int* acc_w = acc + ((threadIdx.x >> 6) % R) * slots;
-
-	// pre-pass: sum over the chunk's points of max_f |dL/dy| -> the fixed-point scale (no entry can
-	// receive more: a point's corner weights sum to 1). A non-finite dL/dy makes the item's gradient NaN.
-	float m = 0.0f;
-	for (uint32_t ib = i0 + threadIdx.x; ib < i1; ib += 4 * blockDim.x) {
-		float dy[4][F];
-#pragma unroll
-		for (uint32_t u = 0; u < 4; ++u) {
-			const uint32_t i = ib + u * blockDim.x;
-			if (i < i1) load_dy_f32<F>(dLdy, dy_stride, it.level, i, dyvec, dy[u]);
-			else {
-#pragma unroll
-				for (uint32_t f = 0; f < F; ++f) dy[u][f] = 0.0f;
-			}
-		}
-#pragma unroll
-		for (uint32_t u = 0; u < 4; ++u) {
-			float s = 0.0f;
-#pragma unroll
-			for (uint32_t f = 0; f < F; ++f) s = __builtin_isfinite(dy[u][f]) ? fmaxf(s, fabsf(dy[u][f])) : __builtin_inff();
-			m += s;
-		}
-	}
-#pragma unroll
-	for (int sh = 32; sh > 0; sh >>= 1) m += __shfl_xor(m, sh);
-	if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-	__syncthreads();
-	m = red[0];
-#pragma unroll
-	for (uint32_t w = 1; w < GRID_BWD_THREADS / 64; ++w) m += red[w];
-	const float P = (float)(i1 > i0 ? i1 - i0 : 1u);
+	const PrecF32 src{dLdy, dy_stride, vec != 0};
+	// 3. layout
+	const AccLayout lay = make_acc_layout(acc, len, nf);
+	zero_accumulators(acc, lay);
+	// 5. the exact pre-pass: sum over the chunk's points of max_f |dL/dy| -> the fixed-point scale (no entry
+	// can receive more: a point's corner weights sum to 1). A non-finite dL/dy makes the item's gradient NaN.
+	const float m = block_sum_waves(dy_bound_sum<PrecF32, F>(src, it.level, f0, nf, i0, i1), red);
 	const bool finite = __builtin_isfinite(m);
-	int e = 0;
-	if (m > 0.0f && finite) {
-		const float lim = (2147483647.0f - (float)(1u << D) * P) / (m * 1.01f);
-		e = ilogbf(lim);
-		e = max(-126, min(e, 126));  // fp32 dL/dy may be tiny: scales up to 2^126 keep its bits
-	}
+	const int e = grid_bwd_scale_exp(m, (float)(i1 > i0 ? i1 - i0 : 1u), D, PrecF32::EXP_MAX);
 	const float scale = ldexpf(1.0f, e);
-
-	uint64_t full = 1;
-	for (uint32_t d = 0; d < D; ++d) full = full * li.res > 0xffffffffull ? 0x100000000ull : full * li.res;
-	const bool whole = it.begin == 0 && len == li.size;
-	const bool pow2 = (li.size & (li.size - 1)) == 0;
-	// the options instantiation (max_level, stochastic interpolation) takes the generic index for every
-	// item: one accumulation body instead of four (which ran it out of scalar registers)
-	if (OPTS)
-		grid_bwd_points_f32<D, F, H, IDX_GENERIC, OPTS>(B, pos, pstride, dLdy, dy_stride, dyvec, it.level, li, hash_grid != 0, interp, it.begin, len, i0, i1, scale, acc_w, o);
-	else if (whole && full <= li.size)
-		grid_bwd_points_f32<D, F, H, IDX_DENSE, OPTS>(B, pos, pstride, dLdy, dy_stride, dyvec, it.level, li, hash_grid != 0, interp, it.begin, len, i0, i1, scale, acc_w, o);
-	else if (whole && hash_grid && pow2)
-		grid_bwd_points_f32<D, F, H, IDX_HASH_POW2, OPTS>(B, pos, pstride, dLdy, dy_stride, dyvec, it.level, li, hash_grid != 0, interp, it.begin, len, i0, i1, scale, acc_w, o);
-	else if (!whole && hash_grid && pow2 && full > li.size)
-		grid_bwd_points_f32<D, F, H, IDX_HASH_RANGE, OPTS>(B, pos, pstride, dLdy, dy_stride, dyvec, it.level, li, hash_grid != 0, interp, it.begin, len, i0, i1, scale, acc_w, o);
-	else
-		grid_bwd_points_f32<D, F, H, IDX_GENERIC, OPTS>(B, pos, pstride, dLdy, dy_stride, dyvec, it.level, li, hash_grid != 0, interp, it.begin, len, i0, i1, scale, acc_w, o);
+	// 6. accumulate
+	with_index_kind<PrecF32::OPTS_ALL_KINDS || !OPTS>(item_index_kind<D>(li, it, hash_grid != 0), [&](auto k) __attribute__((always_inline)) {
+		grid_bwd_points<PrecF32, D, F, H, decltype(k)::value, MODE, OPTS>(src, B, pos, pstride, it.level, li, hash_grid != 0, interp, it.begin, len, f0,
+		                                                                  nf, i0, i1, scale, lay.acc_w, o);
+	});
 	__syncthreads();
-	if (R > 1) {  // merge the replicas into replica 0 (exact: integer sums)
-		if constexpr (F == 2) {
-			long long* a64 = (long long*)acc;
-			for (uint32_t j = threadIdx.x; j < len; j += blockDim.x) {
-				long long t = a64[j];
-				for (uint32_t r = 1; r < R; ++r) t += a64[(size_t)r * len + j];
-				a64[j] = t;
-			}
-		} else {
-			for (uint32_t j = threadIdx.x; j < slots; j += blockDim.x) {
-				int t = acc[j];
-				for (uint32_t r = 1; r < R; ++r) t += acc[(size_t)r * slots + j];
-				acc[j] = t;
-			}
-		}
-		__syncthreads();
-	}
-	// the chunk slab, parameter order: this item's entries [begin, end) x F are one contiguous range
+	// 7. merge
+	merge_replicas(acc, lay, len, MODE == 0);
+	// 8. write the chunk slab, parameter order: this item's entries [begin, end) x F are one contiguous range
 	const float inv = finite ? ldexpf(1.0f, -e) : __builtin_nanf("");
 	float* dst = partial + (size_t)chunk * partial_stride + ((size_t)li.offset + it.begin) * F;
-	const bool al = (((uintptr_t)dst) & 15) == 0;
-	if constexpr (F == 2) {  // decode the packed int32 pairs, two entries per thread (16-byte stores)
-		const long long* a64 = (const long long*)acc;
-		auto dec = [&](long long t) {
-			const int lo = (int)(uint32_t)(unsigned long long)t;
-			const int hi = (int)((t - (long long)lo) >> 32);
-			return make_float2((float)lo * inv, (float)hi * inv);
-		};
-		for (uint32_t j = 2 * threadIdx.x; j < len; j += 2 * blockDim.x) {
-			const float2 a = dec(a64[j]);
-			if (al && j + 1 < len) {
-				const float2 b = dec(a64[j + 1]);
-				*(f4*)(dst + 2 * j) = f4{a.x, a.y, b.x, b.y};
-			} else {
-				dst[2 * j] = a.x;
-				dst[2 * j + 1] = a.y;
-				if (j + 1 < len) {
-					const float2 b = dec(a64[j + 1]);
-					dst[2 * j + 2] = b.x;
-					dst[2 * j + 3] = b.y;
-				}
-			}
-		}
-	} else {
-		for (uint32_t j = 4 * threadIdx.x; j < slots; j += 4 * blockDim.x) {
-			if (al && j + 4 <= slots) {
-				const int4 v = *(const int4*)(acc + j);
-				*(f4*)(dst + j) = f4{(float)v.x * inv, (float)v.y * inv, (float)v.z * inv, (float)v.w * inv};
-			} else {
-				for (uint32_t k = j; k < slots && k < j + 4; ++k) dst[k] = (float)acc[k] * inv;
-			}
-		}
-	}
+	write_slab<SlabStorePlain<PrecF32::SLAB_PAIR_ALIGNED>, MODE == 0>(acc, dst, len, nf, inv);
 }
 
 template <uint32_t D, uint32_t F, HashType H>

@@ -161,6 +161,34 @@ static uint32_t powi_u32(uint32_t base, uint32_t exp) {
 	return r;
 }
 
+// The items of a backward plan must tile [0, size) x [0, F) of each of its levels exactly. An entry in no
+// item is never written by k_grid_bwd_lds, and whatever its slab element held is summed into the
+// gradient. The kernel's IDX_HASH_RANGE index and write_slab's one contiguous run per item assume one
+// of two splits per level: entry ranges holding all F features, or feature groups holding every entry.
+// Either must run 0 -> size (or 0 -> F) without gap or overlap.
+static void check_items_tile_levels(const std::vector<GridSlice>& items, const std::vector<LevelInfo>& levels, uint32_t n_levels, uint32_t F) {
+	std::vector<std::vector<std::pair<uint32_t, uint32_t>>> runs(n_levels);  // [lo, hi) along the level's split axis
+	std::vector<int> by_feature(n_levels, -1);
+	for (const GridSlice& s : items) {
+		TCNN_CHECK(s.level < n_levels && s.begin < s.end && s.end <= levels[s.level].size && s.nf >= 1 && s.f0 + s.nf <= F,
+		           "GridEncoding: backward item outside its level");
+		const bool all_features = s.f0 == 0 && s.nf == F;
+		TCNN_CHECK(all_features || (s.begin == 0 && s.end == levels[s.level].size), "GridEncoding: backward item splits entries and features");
+		TCNN_CHECK(by_feature[s.level] < 0 || by_feature[s.level] == (all_features ? 0 : 1), "GridEncoding: level split two ways");
+		by_feature[s.level] = all_features ? 0 : 1;
+		runs[s.level].push_back(all_features ? std::make_pair(s.begin, s.end) : std::make_pair(s.f0, s.f0 + s.nf));
+	}
+	for (uint32_t l = 0; l < n_levels; ++l) {
+		std::sort(runs[l].begin(), runs[l].end());
+		uint32_t at = 0;
+		for (const auto& r : runs[l]) {
+			TCNN_CHECK(r.first == at, "GridEncoding: backward items of level " + std::to_string(l) + " leave a gap or overlap at " + std::to_string(at));
+			at = r.second;
+		}
+		TCNN_CHECK(at == (by_feature[l] == 1 ? F : levels[l].size), "GridEncoding: backward items do not cover level " + std::to_string(l));
+	}
+}
+
 GridEncodingHost::GridEncodingHost(uint32_t n_dims, const json& enc) {
 	const std::string otype = jval<std::string>(enc, "otype", "Grid");
 	const std::string default_type = ieq(otype, "TiledGrid") ? "Tiled" : (ieq(otype, "DenseGrid") ? "Dense" : "Hash");
@@ -269,7 +297,13 @@ GridEncodingHost::GridEncodingHost(uint32_t n_dims, const json& enc) {
 			if (plan == PLAN_RANGE && hashed_pow2) {
 				uint32_t R = 1;
 				while ((uint64_t)size * F / R > S) R *= 2;
-				R = std::max(R, std::min(sw.grid_bwd_ranges, size / 256));  // tuning override (TCNN_GRID_BWD_RANGES)
+				// tuning override (TCNN_GRID_BWD_RANGES), rounded up to a power of two: R must divide the
+				// (power-of-two) size, or the entries [R * len, size) would be in no item
+				// (clamped to size / 256 first, itself a power of two: the doubling cannot wrap)
+				const uint32_t most = size / 256;
+				uint32_t want = 1;
+				while (want < std::min(sw.grid_bwd_ranges, most)) want *= 2;
+				R = std::max(R, want);
 				const uint32_t len = size / R;
 				for (uint32_t r = 0; r < R; ++r) single.push_back(GridSlice{l, r * len, (r + 1) * len, 0, F});
 				continue;
@@ -285,6 +319,7 @@ GridEncodingHost::GridEncodingHost(uint32_t n_dims, const json& enc) {
 	plans[PLAN_FEATURE].identity = true;
 	for (uint32_t l = 0; l < first_binned; ++l) plans[PLAN_FEATURE].identity = plans[PLAN_FEATURE].identity && map.nf[l] == F;
 	if (!plans[PLAN_RANGE].identity) plans[PLAN_RANGE] = plans[PLAN_FEATURE];  // (no hashed split: one plan)
+	for (const GridPlan& pl : plans) check_items_tile_levels(pl.slices, levels, first_binned, F);
 	map.pbase[first_binned] = n_lds_params;
 	d_slab_map.reserve(sizeof(GridSlabMap));
 	TCNN_HIP_CHECK(hipMemcpy(d_slab_map.p, &map, sizeof(GridSlabMap), hipMemcpyHostToDevice));
@@ -417,6 +452,7 @@ void GridEncodingHost::build_plan_f32() {
 		for (uint32_t b = 0; b < size; b += len) out.push_back(GridSlice{l, b, std::min(size, b + len), 0, F});
 	}
 	for (const GridSlice& s : out) TCNN_CHECK((uint64_t)(s.end - s.begin) * F <= S, "GridEncoding: fp32 backward item exceeds the LDS");
+	check_items_tile_levels(out, levels, desc.n_levels, F);
 	plan_f32.identity = true;
 	plan_f32.d_slices.reserve(out.size() * sizeof(GridSlice));
 	TCNN_HIP_CHECK(hipMemcpy(plan_f32.d_slices.p, out.data(), out.size() * sizeof(GridSlice), hipMemcpyHostToDevice));

@@ -123,6 +123,15 @@ def test_module_grad_config_hash_lds_per_element(torch_mod):
     _check_grid_grad(got, ref, tol, True, "config_hash LDS items")
 
 
+def test_module_grad_config_hash_three_ranges(torch_mod, monkeypatch):
+    """TCNN_GRID_BWD_RANGES=3 is rounded up to 4 entry ranges per hashed level: 3 does not divide the
+    2^15 entries, and the last two of each level would be in no item, their slab elements never
+    written. The plan builder checks that the items tile every level, so the constructor must not throw."""
+    monkeypatch.setenv("TCNN_GRID_BWD_RANGES", "3")
+    got, ref, tol, _ = _module_case(torch_mod, CONFIG_HASH["encoding"], 2, 4096)
+    _check_grid_grad(got, ref, tol, True, "config_hash TCNN_GRID_BWD_RANGES=3")
+
+
 @pytest.mark.parametrize("enc_name", ["config_hash", "log2t19"])
 def test_outlier_dy_keeps_resolution(torch_mod, enc_name):
     """One dL/dy 1000x the others in a chunk: the fixed-point step follows sum |dL/dy|, so the

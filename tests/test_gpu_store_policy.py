@@ -61,6 +61,33 @@ def test_three_steps_bit_identical_to_plain_stores(torch_mod, monkeypatch, B, ou
         _assert_same(trainer_arrays(new), trainer_arrays(old), (B, outside, s))
 
 
+MODE2_ENC = {"otype": "HashGrid", "n_levels": 6, "n_features_per_level": 4, "log2_hashmap_size": 14, "base_resolution": 16,
+             "per_level_scale": 2.0}
+
+
+@pytest.mark.parametrize("B", [256, 16384])
+@pytest.mark.parametrize("case", ["mode2_d2_f4", "mode1_feature_plan"])
+def test_module_grid_grad_bit_identical_to_plain_stores(torch_mod, monkeypatch, case, B):
+    """The unpacked slab writers (write_slab, PACKED = false), which the config_hash step's packed pairs
+    never reach: a D = 2, F = 4 grid (all F features per entry, mode 2: whole dense levels and entry
+    ranges of the hashed ones) and config_hash under the feature plan (one feature per item, mode 1).
+    B = 256: one chunk, replicas on the coarse levels; 16384: two chunks."""
+    from test_gpu_grid_large import _module_grad, _random_dy
+    enc = MODE2_ENC
+    if case == "mode1_feature_plan":
+        enc = CONFIG_HASH["encoding"]
+        monkeypatch.setenv("TCNN_GRID_BWD_PLAN", "feature")
+    pos, _ = _batch(B, 0, True)
+    dy = _random_dy(B, enc["n_levels"], enc["n_features_per_level"], 5)
+    monkeypatch.delenv("TCNN_WT_STORES", raising=False)
+    new = _module_grad(torch_mod, enc, 2, pos, dy)
+    monkeypatch.setenv("TCNN_WT_STORES", "0")
+    old = _module_grad(torch_mod, enc, 2, pos, dy)
+    assert np.count_nonzero(new) > new.size // 100
+    bad = np.flatnonzero(new.view(np.uint32) != old.view(np.uint32))
+    assert bad.size == 0, (case, B, int(bad.size), int(bad[0]), float(new[bad[0]]), float(old[bad[0]]))
+
+
 def test_sequential_readers_of_the_slabs(torch_mod, monkeypatch):
     """training_step(run_optimizer=False) + optimizer_step() read the slabs through the sequential
     reductions (launch_column_sums, reduce_items) instead of the tail and k_adam: with the default
