@@ -17,9 +17,9 @@
  *
  * Matrix conventions (reference common.h:157-167): input fp32 [n x n_input_dims] row-major
  * (= CM [n_input_dims x n]); outputs / params / dL_doutput / dL_dparams / dL_ddLdoutput have the module's
- * precision (tcnn_module_param_precision / _output_precision): fp16 for every network module, fp16 or
- * fp32 for an encoding module as it was created; n must be a multiple of tcnn_batch_size_granularity()
- * (256) for networks (encoding modules take any n).
+ * precision (tcnn_module_param_precision / _output_precision): fp16 or fp32, as the module was created
+ * (fp16 from every constructor that takes no precision); n must be a multiple of
+ * tcnn_batch_size_granularity() (256) for networks (encoding modules take any n).
  */
 #ifndef TCNN_MI355X_H
 #define TCNN_MI355X_H
@@ -69,6 +69,17 @@ tcnn_module* tcnn_create_network_with_input_encoding(uint32_t n_input_dims, uint
                                                      const char* encoding_json, const char* network_json);
 /* cpp::create_network(n_input_dims, n_output_dims, network) (= Identity encoding + network) */
 tcnn_module* tcnn_create_network(uint32_t n_input_dims, uint32_t n_output_dims, const char* network_json);
+/* The two constructors above with the module's precision. TCNN_PRECISION_FP16: exactly the module they
+   create. TCNN_PRECISION_FP32: a network whose parameters ([network | encoding], the fp16 module's layout,
+   count and initial values), output rows [n][padded n_output_dims], dL_doutput, dL_dparams and every
+   activation in between are fp32 -- the fp32 encoding's rows go to the first layer as they are, the layers run
+   on the f32 matrix cores, nothing is narrowed to fp16. n_neurons: any multiple of 16; FullyFusedMLP (16 /
+   32 / 64 / 128 neurons, as at fp16) and CutlassMLP run the same kernels; every activation the fp16 module
+   trains, and Sine through tcnn_module_inference only. The default loss scale is
+   tcnn_default_loss_scale(TCNN_PRECISION_FP32). Any other precision fails. */
+tcnn_module* tcnn_create_network_with_input_encoding_precision(uint32_t n_input_dims, uint32_t n_output_dims,
+                                                               const char* encoding_json, const char* network_json, int precision);
+tcnn_module* tcnn_create_network_precision(uint32_t n_input_dims, uint32_t n_output_dims, const char* network_json, int precision);
 /* cpp::create_encoding(n_input_dims, encoding, requested_precision): TCNN_PRECISION_FP16, or
    TCNN_PRECISION_FP32 for a module whose parameters, output rows, dL_doutput and dL_dparams are fp32 with
    fp32 arithmetic in between (nothing narrowed to fp16; create_encoding<float>, Encoding(dtype=float32)).
@@ -94,7 +105,7 @@ int tcnn_module_backward(tcnn_module* m, void* stream, const tcnn_context* ctx, 
  * rounded to fp16, the module's backward runs on it, dL_dinput (fp32) is divided by loss_scale and
  * dL_dparams = fp16(fp16 gradient / loss_scale) -- stored as fp16, or widened to fp32 when
  * dparams_fp32 (the gradient of fp32 master parameters cast to fp16 for the module) -- the same
- * values the binding computes with three torch operations. An Fp32 encoding module does the same three
+ * values the binding computes with three torch operations. An Fp32 module (encoding or network) does the same three
  * steps in fp32 (dL_doutput * loss_scale, backward, both gradients divided by loss_scale); its dL_dparams
  * is fp32 whatever dparams_fp32 says. */
 int tcnn_module_backward_scaled(tcnn_module* m, void* stream, const tcnn_context* ctx, uint32_t n, float* dL_dinput,
@@ -125,7 +136,7 @@ uint32_t tcnn_module_n_output_dims(const tcnn_module* m); /* padded width (cpp_a
 uint64_t tcnn_module_n_params(const tcnn_module* m);
 /* of which the network's (matrix) parameters, which come first: 0 for an encoding module */
 uint64_t tcnn_module_n_network_params(const tcnn_module* m);
-/* the module's own precision (TCNN_PRECISION_*): Fp32 for an encoding created with it, else Fp16 */
+/* the module's own precision (TCNN_PRECISION_*): Fp32 for an encoding or a network created with it, else Fp16 */
 int tcnn_module_param_precision(const tcnn_module* m);
 int tcnn_module_output_precision(const tcnn_module* m);
 /* Module::initialize_params(seed, params_full_precision, scale): pcg32{seed} (cpp_api.cu:133-136);

@@ -161,6 +161,18 @@ inline Module* create_network_with_input_encoding(uint32_t n_input_dims, uint32_
 inline Module* create_network(uint32_t n_input_dims, uint32_t n_output_dims, const json& network) {
 	return new detail::NativeModule(tcnn_create_network(n_input_dims, n_output_dims, network.dump().c_str()));
 }
+// The same two with the module's precision: Fp16 is the module above, Fp32 an fp32 network module (parameters,
+// output, dL/doutput and dL/dparams fp32; param_precision() and output_precision() report it).
+inline Module* create_network_with_input_encoding(uint32_t n_input_dims, uint32_t n_output_dims, const json& encoding,
+                                                  const json& network, Precision precision) {
+	return new detail::NativeModule(tcnn_create_network_with_input_encoding_precision(
+	    n_input_dims, n_output_dims, encoding.dump().c_str(), network.dump().c_str(),
+	    precision == Precision::Fp16 ? TCNN_PRECISION_FP16 : TCNN_PRECISION_FP32));
+}
+inline Module* create_network(uint32_t n_input_dims, uint32_t n_output_dims, const json& network, Precision precision) {
+	return new detail::NativeModule(tcnn_create_network_precision(n_input_dims, n_output_dims, network.dump().c_str(),
+	                                                              precision == Precision::Fp16 ? TCNN_PRECISION_FP16 : TCNN_PRECISION_FP32));
+}
 inline Module* create_encoding(uint32_t n_input_dims, const json& encoding, Precision requested_precision) {
 	return new detail::NativeModule(tcnn_create_encoding(
 	    n_input_dims, encoding.dump().c_str(), requested_precision == Precision::Fp16 ? TCNN_PRECISION_FP16 : TCNN_PRECISION_FP32));

@@ -110,7 +110,7 @@ struct ModuleBase {
 	}
 	virtual GridEncodingHost* grid_encoding() { return nullptr; }
 	// precision of the parameters, the output, dL/doutput and dL/dparams (TCNN_PRECISION_*): fp16 for
-	// every module but an encoding created with Fp32
+	// every module but an encoding or a network created with Fp32
 	virtual int precision() const { return TCNN_PRECISION_FP16; }
 	size_t elem_bytes() const { return precision() == TCNN_PRECISION_FP32 ? 4 : 2; }
 	virtual const char* engine() const { return "encoding"; }
@@ -202,6 +202,78 @@ struct ModuleNWIE : ModuleBase {
 	const char* engine() const override { return model.engine(); }
 	const char* inference_engine() const override { return model.inference_engine(); }
 	const char* backward_kernel(bool with_dinput) const override { return model.backward_kernel(with_dinput); }
+	uint32_t n_input_dims() const override { return model.n_input_dims; }
+	uint32_t n_output_dims() const override { return model.mlp.padded_output; }
+	uint64_t n_params() const override { return model.n_params(); }
+	uint64_t n_network_params() const override { return model.mlp.n_params(); }
+	void initialize_params(uint64_t seed, float* p, float scale) override {
+		Pcg32 rng{seed};
+		std::vector<float> host(n_params());
+		model.initialize_params(rng, host.data(), scale);
+		TCNN_HIP_CHECK(hipMemcpy(p, host.data(), host.size() * 4, hipMemcpyHostToDevice));
+	}
+	json hyperparams() const override { return model.hyperparams(); }
+	std::string name() const override { return "NetworkWithInputEncoding"; }
+};
+
+// NetworkWithInputEncoding at fp32 precision (tcnn_create_network*_precision with Fp32): parameters, output,
+// dL/doutput, dL/dparams fp32, on the f32-MFMA layer kernels behind the fp32 encoding. The forward's context
+// keeps the encoded rows, every hidden activation and the output; TCNN_NO_FORWARD_KEEP (or a backward that sees
+// other inputs or parameters than the forward) recomputes them.
+struct NwieF32Ctx : ModuleCtx {
+	std::shared_ptr<KeepPool> pool;
+	std::unique_ptr<DevBuf> keep;
+	const float* in = nullptr;
+	const void* params = nullptr;
+	~NwieF32Ctx() override {
+		if (pool && keep) pool->put(std::move(keep));
+	}
+};
+
+struct ModuleNWIEF32 : ModuleBase {
+	NetworkF32Host model;
+	DevBuf rekeep;
+	std::shared_ptr<KeepPool> pool = std::make_shared<KeepPool>();
+	ModuleNWIEF32(uint32_t n_in, uint32_t n_out, const json& enc, const json& net) : model(n_in, n_out, enc, net) {}
+	int precision() const override { return TCNN_PRECISION_FP32; }
+	void inference(hipStream_t st, uint32_t n, const float* in, void* out, const void* params) override {
+		check_batch(n);
+		model.forward(st, n, in, (const float*)params, (float*)out, nullptr);
+	}
+	std::unique_ptr<ModuleCtx> forward(hipStream_t st, uint32_t n, const float* in, void* out, const void* params, bool) override {
+		check_batch(n);
+		TCNN_CHECK(!model.has_sine(), "Sine has no backward from its forward value: a forward that keeps a context is refused (use inference)");
+		auto c = std::make_unique<NwieF32Ctx>();
+		if (model.sw.no_forward_keep) {  // A/B switch (read when the module is built): the backward recomputes the forward
+			model.forward(st, n, in, (const float*)params, (float*)out, nullptr);
+			return c;
+		}
+		c->pool = pool;
+		c->keep = pool->get();
+		c->keep->reserve(model.keep_floats(n) * 4);
+		model.forward(st, n, in, (const float*)params, (float*)out, c->keep->as<float>());
+		c->in = in;
+		c->params = params;
+		return c;
+	}
+	void backward(hipStream_t st, const ModuleCtx* ctx, uint32_t n, float* dL_din, const void* dL_dout, void* dL_dparams, const float* in,
+	              const void*, const void* params) override {
+		check_batch(n);
+		if (!dL_dparams && !dL_din) return;
+		// the kept activations describe this batch only if the backward sees the forward's input and parameters
+		const NwieF32Ctx* c = dynamic_cast<const NwieF32Ctx*>(ctx);
+		const float* keep = c && c->keep && c->in == in && c->params == params ? c->keep->as<float>() : nullptr;
+		if (!keep) {
+			rekeep.reserve(model.keep_floats(n) * 4);
+			model.forward(st, n, in, (const float*)params, nullptr, rekeep.as<float>());
+			keep = rekeep.as<float>();
+		}
+		model.backward(st, n, in, (const float*)params, (const float*)dL_dout, keep, (float*)dL_dparams, dL_din);
+	}
+	GridEncodingHost* grid_encoding() override { return model.enc->lone_grid(); }
+	const char* engine() const override { return "layered"; }
+	const char* inference_engine() const override { return "layered"; }
+	const char* backward_kernel(bool) const override { return "layered"; }
 	uint32_t n_input_dims() const override { return model.n_input_dims; }
 	uint32_t n_output_dims() const override { return model.mlp.padded_output; }
 	uint64_t n_params() const override { return model.n_params(); }
@@ -364,6 +436,31 @@ tcnn_module* tcnn_create_network(uint32_t n_in, uint32_t n_out, const char* net)
 		auto* r = new tcnn_module;
 		r->m = std::make_unique<ModuleNWIE>(n_in, n_out, json{{"otype", "Identity"}}, parse_json(net));
 		return r;
+	});
+}
+
+// The two constructors with the module's precision: Fp16 is the module the constructors above create, Fp32
+// an fp32 network module (ModuleNWIEF32).
+tcnn_module* tcnn_create_network_with_input_encoding_precision(uint32_t n_in, uint32_t n_out, const char* enc, const char* net,
+                                                               int precision) {
+	return guard_ptr<tcnn_module>([&] {
+		TCNN_CHECK(precision == TCNN_PRECISION_FP16 || precision == TCNN_PRECISION_FP32,
+		           "create_network_with_input_encoding: precision must be Fp16 or Fp32");
+		auto r = std::make_unique<tcnn_module>();
+		if (precision == TCNN_PRECISION_FP32) r->m = std::make_unique<ModuleNWIEF32>(n_in, n_out, parse_json(enc), parse_json(net));
+		else r->m = std::make_unique<ModuleNWIE>(n_in, n_out, parse_json(enc), parse_json(net));
+		return r.release();
+	});
+}
+
+tcnn_module* tcnn_create_network_precision(uint32_t n_in, uint32_t n_out, const char* net, int precision) {
+	return guard_ptr<tcnn_module>([&] {
+		TCNN_CHECK(precision == TCNN_PRECISION_FP16 || precision == TCNN_PRECISION_FP32, "create_network: precision must be Fp16 or Fp32");
+		auto r = std::make_unique<tcnn_module>();
+		const json identity = json{{"otype", "Identity"}};
+		if (precision == TCNN_PRECISION_FP32) r->m = std::make_unique<ModuleNWIEF32>(n_in, n_out, identity, parse_json(net));
+		else r->m = std::make_unique<ModuleNWIE>(n_in, n_out, identity, parse_json(net));
+		return r.release();
 	});
 }
 

@@ -419,6 +419,20 @@ void launch_grid_bwd_f32(hipStream_t st, const GridCall& g, uint32_t B, const fl
                          uint32_t dy_stride, const GridSlice* slices, uint32_t n_slices, uint32_t n_chunks, float* partial,
                          uint32_t partial_stride);
 
+// ---- fp32 network modules (Network / NetworkWithInputEncoding dtype = float32; mlp_f32.hip): the layer-wise
+// engine on the f32 MFMA. Weights [N][K], rows AoS [B][width], all fp32; N and K multiples of 16, B of 128. ----
+// y[B][N] = act(x[B][K] w^T)
+void launch_f32_layer_fwd(hipStream_t st, uint32_t B, uint32_t N, uint32_t K, const float* w, const float* x, float* y, int act);
+// dx[B][K] = (dy[B][N] o act'(yv)) w; yv: the forward value beside dy (unread for ACT_NONE). The transfer runs in the operand load.
+void launch_f32_layer_bwd(hipStream_t st, uint32_t B, uint32_t N, uint32_t K, const float* w, const float* dy, const float* yv, int act,
+                          float* dx);
+// partial[slab][N][K] = sum over the slab's rows of (dy o act'(yv))^T x; f32_wgrad_n_slabs(B) slabs of
+// f32_wgrad_slab_rows(B) rows, which launch_reduce_partials sums in a fixed order
+uint32_t f32_wgrad_slab_rows(uint32_t B);
+uint32_t f32_wgrad_n_slabs(uint32_t B);
+void launch_f32_wgrad(hipStream_t st, uint32_t B, uint32_t N, uint32_t K, const float* dy, const float* yv, int act, const float* x,
+                      float* partial);
+
 void launch_probe_hfma(hipStream_t st, const void* a, const void* b, const void* c, void* out, uint32_t n_pairs);
 // Diagnostic: the config_hash fused (pipelined) kernel with s_memtime phase stamps (prof: [blocks*8][8] u64).
 void launch_fused_train_profile(hipStream_t st, uint32_t B, uint32_t dims, const void* params16, const void* table16,

@@ -1276,6 +1276,94 @@ void NetworkHost::fwd_bwd_layered(hipStream_t st, StepWorkspace& ws, const Train
 }
 
 // ------------------------------------------------------------------------------------------
+// NetworkWithInputEncoding<float> (an fp32 network module; mlp_f32.hip)
+// ------------------------------------------------------------------------------------------
+NetworkF32Host::NetworkF32Host(uint32_t n_in, uint32_t n_out, const json& e, const json& net) : n_input_dims(n_in), n_output_dims(n_out) {
+	enc = std::make_unique<EncodingHost>(n_in, e, true);
+	enc->set_alignment(16);
+	mlp = MlpHost(enc->padded_output_width(), n_out, net);
+	TCNN_CHECK(mlp.width % 16 == 0 && mlp.width > 0, "fp32 network: n_neurons must be a multiple of 16, got " + std::to_string(mlp.width));
+}
+
+void NetworkF32Host::initialize_params(Pcg32& rng, float* out, float scale) const {
+	mlp.initialize_params(rng, out, scale);
+	enc->initialize_params(rng, out + mlp.n_params(), scale);
+}
+
+json NetworkF32Host::hyperparams() const {
+	return {{"otype", "NetworkWithInputEncoding"}, {"encoding", enc->hyperparams()}, {"network", mlp.hyperparams()}};
+}
+
+void NetworkF32Host::forward(hipStream_t st, uint32_t B, const float* pos, const float* params, float* out32, float* keep) {
+	const uint32_t W = mlp.width, IN = mlp.n_input, NH = mlp.n_hidden_layers, OUTP = mlp.padded_output;
+	if (!keep) acts.reserve(((size_t)B * IN + 2 * (size_t)B * W) * 4);
+	float* e = keep ? keep : acts.as<float>();
+	float* h = e + (size_t)B * IN;
+	auto act_buf = [&](uint32_t j) { return h + (size_t)(keep ? j : (j & 1)) * B * W; };
+	enc->forward_aos(st, B, pos, params + mlp.n_params(), e);
+	const float* p = params;
+	const float* x = e;
+	uint32_t K = IN;
+	for (uint32_t j = 0; j < NH; ++j) {
+		launch_f32_layer_fwd(st, B, W, K, p, x, act_buf(j), mlp.activation);
+		p += (size_t)W * K;
+		x = act_buf(j);
+		K = W;
+	}
+	// with a keep the output lands there (the backward's output-activation transfer reads it) and is copied out
+	float* y = keep ? h + (size_t)NH * B * W : out32;
+	launch_f32_layer_fwd(st, B, OUTP, K, p, x, y, mlp.output_activation);
+	if (keep && out32) TCNN_HIP_CHECK(hipMemcpyAsync(out32, y, (size_t)B * OUTP * 4, hipMemcpyDeviceToDevice, st));
+}
+
+void NetworkF32Host::backward(hipStream_t st, uint32_t B, const float* pos, const float* params, const float* dout32, const float* keep,
+                              float* dL_dparams, float* dL_dinput) {
+	TCNN_CHECK(!has_sine(), "Sine has no backward from its forward value: the MI355X engine serves it through inference only");
+	const uint32_t W = mlp.width, IN = mlp.n_input, NH = mlp.n_hidden_layers, OUTP = mlp.padded_output;
+	const uint32_t n_mlp = mlp.n_params();
+	const float* e = keep;
+	const float* h = e + (size_t)B * IN;
+	auto act = [&](uint32_t j) { return h + (size_t)j * B * W; };
+	const float* y = h + (size_t)NH * B * W;
+	const float* eparams = params + n_mlp;
+	const uint32_t nsl = f32_wgrad_n_slabs(B);
+	const uint32_t maxK = std::max(W, IN);
+	delta0.reserve((size_t)B * maxK * 4);
+	delta1.reserve((size_t)B * maxK * 4);
+	if (dL_dparams) wgrad_partial.reserve((size_t)nsl * std::max(W, OUTP) * maxK * 4);
+	// weight offsets [W0 | W1 .. W_{NH-1} | Wout] ([Wout] alone for 0 hidden layers)
+	auto w_off = [&](uint32_t j) -> size_t { return j == 0 ? 0 : (size_t)W * IN + (size_t)(j - 1) * W * W; };
+	// dW = (dy o act'(yv))^T x: per-slab partial sums, then their fixed-order sum
+	auto wgrad = [&](uint32_t N, uint32_t K, const float* dy, const float* yv, int a, const float* x, size_t off) {
+		if (!dL_dparams) return;
+		launch_f32_wgrad(st, B, N, K, dy, yv, a, x, wgrad_partial.as<float>());
+		const size_t tf = reduce_partials_tmp_floats(nsl, N * K);
+		if (tf) red_tmp.reserve(tf * 4);
+		launch_reduce_partials(st, wgrad_partial.as<float>(), nsl, N * K, N * K, dL_dparams + off, red_tmp.as<float>());
+	};
+	float* dcur = delta0.as<float>();
+	float* dnext = delta1.as<float>();
+	const bool enc_grad = (dL_dparams && enc->n_params() > 0) || dL_dinput;
+	// a delta here is dL/d(post-activation value): both of its readers apply the transfer as they load it
+	if (NH == 0) {
+		wgrad(OUTP, IN, dout32, y, mlp.output_activation, e, 0);
+		if (enc_grad) launch_f32_layer_bwd(st, B, OUTP, IN, params, dout32, y, mlp.output_activation, dnext);
+	} else {
+		wgrad(OUTP, W, dout32, y, mlp.output_activation, act(NH - 1), w_off(NH));
+		launch_f32_layer_bwd(st, B, OUTP, W, params + w_off(NH), dout32, y, mlp.output_activation, dcur);
+		for (uint32_t j = NH - 1; j >= 1; --j) {
+			wgrad(W, W, dcur, act(j), mlp.activation, act(j - 1), w_off(j));
+			launch_f32_layer_bwd(st, B, W, W, params + w_off(j), dcur, act(j), mlp.activation, dnext);
+			std::swap(dcur, dnext);
+		}
+		wgrad(W, IN, dcur, act(0), mlp.activation, e, 0);
+		if (enc_grad) launch_f32_layer_bwd(st, B, W, IN, params, dcur, act(0), mlp.activation, dnext);
+	}
+	if (dL_dinput) enc->backward_input(st, B, pos, dnext, dL_dinput, eparams, 2);
+	if (dL_dparams && enc->n_params() > 0) enc->backward_params(st, B, pos, dnext, 2, dL_dparams + n_mlp);
+}
+
+// ------------------------------------------------------------------------------------------
 // Trainer (reference trainer.h:47-361, config.h:46-63)
 // ------------------------------------------------------------------------------------------
 TrainerHost::TrainerHost(uint32_t n_in, uint32_t n_out, const json& cfg, uint32_t seed)

@@ -281,7 +281,8 @@ struct EncodingHost {
 	// Precision of the parameters, the encoded rows and dL/dy (create_encoding<T>): fp16, or fp32 for an
 	// fp32 encoding module, whose every buffer named "16" below then holds fp32 and whose kernels are the
 	// fp32 ones (nothing narrowed to fp16). Layout, widths, alignment, parameter offsets, initial
-	// parameters, hyperparams() and name() do not depend on it. Networks always build fp16 encodings.
+	// parameters, hyperparams() and name() do not depend on it. fp16 networks and the Trainer build fp16 encodings,
+	// an fp32 network module (NetworkF32Host) an fp32 one.
 	bool f32 = false;
 
 	// Widths follow composite.h:188-198: every part is created with alignment 1, part i is widened so
@@ -491,6 +492,33 @@ private:
 	const void* weight_image(hipStream_t st, StepWorkspace& ws, const void* params16, bool have_image);
 	// forward through the layers from ws.enc16; hidden activations kept in ws.acts when `keep`
 	void forward_layers(hipStream_t st, StepWorkspace& ws, uint32_t B, const void* params16, void* out16, bool keep);
+};
+
+// NetworkWithInputEncoding<float>: an fp32 network module (Network / NetworkWithInputEncoding dtype = float32).
+// The fp32 EncodingHost in front, its rows handed to the first layer as they are, then one f32-MFMA kernel per
+// layer (mlp_f32.hip). Parameters [mlp | encoding], rows, dL/dy, dL/dparams and dL/dinput are all fp32; layout,
+// parameter count, initial values, hyperparams() follow NetworkHost for the same config. FullyFusedMLP and
+// CutlassMLP run the same kernels. Sine (no backward from its forward value) is served by inference() only.
+struct NetworkF32Host {
+	EngineSwitches sw = EngineSwitches::from_env();
+	std::unique_ptr<EncodingHost> enc;
+	MlpHost mlp;
+	uint32_t n_input_dims = 0, n_output_dims = 0;
+	DevBuf acts, delta0, delta1, wgrad_partial, red_tmp;  // grow-only scratch
+	NetworkF32Host(uint32_t n_in, uint32_t n_out, const json& enc, const json& net);
+	uint64_t n_params() const { return (uint64_t)mlp.n_params() + enc->n_params(); }
+	bool has_sine() const { return mlp.activation == ACT_SINE || mlp.output_activation == ACT_SINE; }
+	void initialize_params(Pcg32& rng, float* host_out, float scale = 1.0f) const;
+	json hyperparams() const;
+	// what a forward keeps for its backward: [enc B x IN | NH hidden activations B x W | output B x OUTP] floats
+	size_t keep_floats(uint32_t B) const {
+		return (size_t)B * ((size_t)mlp.n_input + (size_t)mlp.n_hidden_layers * mlp.width + mlp.padded_output);
+	}
+	// out32 fp32 [B][padded_output]; keep (nullable): keep_floats(B) floats, else two ping-pong buffers of the scratch
+	void forward(hipStream_t st, uint32_t B, const float* pos, const float* params, float* out32, float* keep);
+	// from a forward's keep: dL/dparams fp32 [n_params()] (nullable), dL/dinput fp32 [B][n_input_dims] (nullable)
+	void backward(hipStream_t st, uint32_t B, const float* pos, const float* params, const float* dout32, const float* keep,
+	              float* dL_dparams, float* dL_dinput);
 };
 
 // One RCCL communicator of a data-parallel job (dp.cpp): rank `rank` of `nranks`, one process per

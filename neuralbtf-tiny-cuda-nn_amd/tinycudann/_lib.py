@@ -33,6 +33,8 @@ _SIGS = {
     "tcnn_generate_random_logistic": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_float, c_float]),
     "tcnn_create_network_with_input_encoding": (c_void_p, [c_uint32, c_uint32, c_char_p, c_char_p]),
     "tcnn_create_network": (c_void_p, [c_uint32, c_uint32, c_char_p]),
+    "tcnn_create_network_with_input_encoding_precision": (c_void_p, [c_uint32, c_uint32, c_char_p, c_char_p, c_int]),
+    "tcnn_create_network_precision": (c_void_p, [c_uint32, c_uint32, c_char_p, c_int]),
     "tcnn_create_encoding": (c_void_p, [c_uint32, c_char_p, c_int]),
     "tcnn_create_encoding_aligned": (c_void_p, [c_uint32, c_char_p, c_int, c_uint32]),
     "tcnn_module_destroy": (None, [c_void_p]),

@@ -354,34 +354,50 @@ class Module(torch.nn.Module):
                 f"dtype={self.dtype}, hyperparams={self.native_tcnn_module.hyperparams()}")
 
 
+def _network_precision(dtype, who):
+    """dtype=None / torch.float16: the fp16 module; torch.float32: the fp32 module (parameters, output and
+    gradients fp32, f32 matrix-core kernels)"""
+    if dtype is None or dtype == torch.float16:
+        return PRECISION_FP16
+    if dtype == torch.float32:
+        return PRECISION_FP32
+    raise ValueError(f"{who} only supports fp32 or fp16 precision, but got {dtype}")
+
+
 class NetworkWithInputEncoding(Module):
-    def __init__(self, n_input_dims, n_output_dims, encoding_config, network_config, seed=1337):
+    def __init__(self, n_input_dims, n_output_dims, encoding_config, network_config, seed=1337, dtype=None):
         if not _C.has_networks():
             raise RuntimeError("Cannot create `NetworkWithInputEncoding` because tiny-cuda-nn was not compiled with neural network support.")
         self.n_input_dims = n_input_dims
         self.n_output_dims = n_output_dims
         self.encoding_config = encoding_config
         self.network_config = network_config
+        self.precision = _network_precision(dtype, "NetworkWithInputEncoding")
         super().__init__(seed=seed)
 
     def _native_tcnn_module(self):
-        return _NativeModule(L.lib().tcnn_create_network_with_input_encoding(
-            self.n_input_dims, self.n_output_dims, json.dumps(self.encoding_config).encode(),
-            json.dumps(self.network_config).encode()))
+        enc, net = json.dumps(self.encoding_config).encode(), json.dumps(self.network_config).encode()
+        if getattr(self, "precision", PRECISION_FP16) == PRECISION_FP16:  # (a pickle from before `precision`: fp16)
+            return _NativeModule(L.lib().tcnn_create_network_with_input_encoding(self.n_input_dims, self.n_output_dims, enc, net))
+        return _NativeModule(L.lib().tcnn_create_network_with_input_encoding_precision(
+            self.n_input_dims, self.n_output_dims, enc, net, self.precision))
 
 
 class Network(Module):
-    def __init__(self, n_input_dims, n_output_dims, network_config, seed=1337):
+    def __init__(self, n_input_dims, n_output_dims, network_config, seed=1337, dtype=None):
         if not _C.has_networks():
             raise RuntimeError("Cannot create `Network` because tiny-cuda-nn was not compiled with neural network support.")
         self.n_input_dims = n_input_dims
         self.n_output_dims = n_output_dims
         self.network_config = network_config
+        self.precision = _network_precision(dtype, "Network")
         super().__init__(seed=seed)
 
     def _native_tcnn_module(self):
-        return _NativeModule(L.lib().tcnn_create_network(self.n_input_dims, self.n_output_dims,
-                                                          json.dumps(self.network_config).encode()))
+        net = json.dumps(self.network_config).encode()
+        if getattr(self, "precision", PRECISION_FP16) == PRECISION_FP16:
+            return _NativeModule(L.lib().tcnn_create_network(self.n_input_dims, self.n_output_dims, net))
+        return _NativeModule(L.lib().tcnn_create_network_precision(self.n_input_dims, self.n_output_dims, net, self.precision))
 
 
 class Encoding(Module):
