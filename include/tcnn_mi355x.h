@@ -113,9 +113,17 @@ int tcnn_module_backward_scaled(tcnn_module* m, void* stream, const tcnn_context
                                 const void* params, float loss_scale, int dparams_fp32);
 /* Module::backward_backward_input(stream, ctx, n, dL_ddLdinput, input, dL_doutput?, dL_dparams?,
  * dL_ddLdoutput?, dL_dinput?, params) (cpp_api.h:94): second-order gradients from dL/d(dL/dinput)
- * fp32 [n][n_input_dims]. Implemented by grid encodings (grid.h:902-1026); every other module
- * fails like the reference's DifferentiableObject (object.h:278-288). Returns without work when
- * both dL_ddLdoutput and dL_dparams are NULL (grid.h:913-915). */
+ * fp32 [n][n_input_dims]. Implemented by grid encodings (grid.h:902-1026), which return without work
+ * when both dL_ddLdoutput and dL_dparams are NULL (grid.h:913-915), and -- beyond the reference --
+ * by Fp32 network modules whose encoding is Identity (a network alone) or a grid standing alone.
+ * Every other module fails like the reference's DifferentiableObject (object.h:278-288), "not
+ * implemented".
+ * On an Fp32 network module: every non-NULL output is overwritten (dL_dparams fp32 [network | encoding],
+ * dL_ddLdoutput fp32 [n][n_output_dims], dL_dinput fp32 [n][n_input_dims]); all three NULL returns
+ * without work; dL_doutput may be NULL only when dL_dparams and dL_dinput are (dL_ddLdoutput does not
+ * depend on it), otherwise the call fails. A context whose forward saw another input or parameter
+ * pointer recomputes the forward. The network's part of dL_dparams is bit-reproducible; a grid's part
+ * is summed with fp32 atomics and is not. */
 int tcnn_module_backward_backward_input(tcnn_module* m, void* stream, const tcnn_context* ctx, uint32_t n,
                                         const float* dL_ddLdinput, const float* input, const void* dL_doutput,
                                         void* dL_dparams, void* dL_ddLdoutput, float* dL_dinput, const void* params);

@@ -49,6 +49,26 @@ __device__ __forceinline__ float act_factor_f32(int a, float y) {
 	}
 }
 
+// d^2 act / d z^2 in the forward value y: the curvature the second-order input gradient needs. Zero for
+// None, ReLU and LeakyReLU. Squareplus: K z = t - 1 / t with t = K y.
+__device__ __forceinline__ float act_factor2_f32(int a, float y) {
+	switch (a) {
+		case AF32_EXPONENTIAL: return y;
+		case AF32_SIGMOID: return (y * (1.0f - y)) * (1.0f - 2.0f * y);
+		case AF32_SQUAREPLUS: {
+			const float t = y * K_ACT_F32;
+			const float t2 = t * t, d = t2 + 1.0f;
+			return (2.0f * K_ACT_F32) * (t2 * t) / ((d * d) * d);
+		}
+		case AF32_SOFTPLUS: {
+			const float e = expf(-y * K_ACT_F32);
+			return K_ACT_F32 * ((1.0f - e) * e);
+		}
+		case AF32_TANH: return (-2.0f * y) * (1.0f - y * y);
+		default: return 0.0f;
+	}
+}
+
 __device__ __forceinline__ float act_bwd_f32(int a, float g, float y) {
 	if (a == AF32_NONE) return g;
 	if (a == AF32_RELU) return y > 0.0f ? g : 0.0f;

@@ -103,9 +103,10 @@ struct ModuleBase {
 	                             const void*, float, bool) {
 		return false;
 	}
-	// object.h:278-288: only encodings that define it (the grid) support second-order gradients
-	virtual void backward_backward_input(hipStream_t, uint32_t, const float*, const float*, const void*, void*, void*, float*,
-	                                     const void*) {
+	// object.h:278-288: only encodings that define it (the grid) support second-order gradients; beyond the
+	// reference, an fp32 network module does too (ModuleNWIEF32)
+	virtual void backward_backward_input(hipStream_t, const ModuleCtx*, uint32_t, const float*, const float*, const void*, void*, void*,
+	                                     float*, const void*) {
 		throw std::runtime_error("DifferentiableObject::backward_backward_input_impl: not implemented error");
 	}
 	virtual GridEncodingHost* grid_encoding() { return nullptr; }
@@ -260,15 +261,29 @@ struct ModuleNWIEF32 : ModuleBase {
 	              const void*, const void* params) override {
 		check_batch(n);
 		if (!dL_dparams && !dL_din) return;
-		// the kept activations describe this batch only if the backward sees the forward's input and parameters
+		model.backward(st, n, in, (const float*)params, (const float*)dL_dout, kept(st, ctx, n, in, params), (float*)dL_dparams, dL_din);
+	}
+	// the context's activations if they describe this batch (the backward sees the forward's input and parameters),
+	// else the forward again into the module's own buffer
+	const float* kept(hipStream_t st, const ModuleCtx* ctx, uint32_t n, const float* in, const void* params) {
 		const NwieF32Ctx* c = dynamic_cast<const NwieF32Ctx*>(ctx);
-		const float* keep = c && c->keep && c->in == in && c->params == params ? c->keep->as<float>() : nullptr;
-		if (!keep) {
-			rekeep.reserve(model.keep_floats(n) * 4);
-			model.forward(st, n, in, (const float*)params, nullptr, rekeep.as<float>());
-			keep = rekeep.as<float>();
-		}
-		model.backward(st, n, in, (const float*)params, (const float*)dL_dout, keep, (float*)dL_dparams, dL_din);
+		if (c && c->keep && c->in == in && c->params == params) return c->keep->as<float>();
+		rekeep.reserve(model.keep_floats(n) * 4);
+		model.forward(st, n, in, (const float*)params, nullptr, rekeep.as<float>());
+		return rekeep.as<float>();
+	}
+	// Second order with respect to the input (beyond the reference, whose networks have none): every non-null
+	// output is overwritten; dL_dout may be null only for the tangent pass alone (dL_ddLdout)
+	void backward_backward_input(hipStream_t st, const ModuleCtx* ctx, uint32_t n, const float* dL_ddLdin, const float* in,
+	                             const void* dL_dout, void* dL_dparams, void* dL_ddLdout, float* dL_din, const void* params) override {
+		check_batch(n);
+		model.check_second_order();
+		if (!dL_dparams && !dL_ddLdout && !dL_din) return;
+		TCNN_CHECK(dL_dout || (!dL_dparams && !dL_din),
+		           "backward_backward_input: dL_doutput may be null only when dL_dparams and dL_dinput are (the tangent pass alone)");
+		TCNN_CHECK(params && in && dL_ddLdin, "backward_backward_input needs the input, the parameters and dL_ddLdinput");
+		model.backward_backward_input(st, n, in, (const float*)params, dL_ddLdin, (const float*)dL_dout, kept(st, ctx, n, in, params),
+		                              (float*)dL_dparams, (float*)dL_ddLdout, dL_din);
 	}
 	GridEncodingHost* grid_encoding() override { return model.enc->lone_grid(); }
 	const char* engine() const override { return "layered"; }
@@ -315,10 +330,10 @@ struct ModuleEncoding : ModuleBase {
 		launch_cast_f32_f16(st, grad32.as<float>(), dL_dparams, enc.n_params());
 	}
 	// a grid standing alone; grids nested in a composite keep ModuleBase's "not implemented"
-	void backward_backward_input(hipStream_t st, uint32_t n, const float* dL_ddLdin, const float* in, const void* dL_dout,
-	                             void* dL_dparams, void* dL_ddLdout, float* dL_din, const void* params) override {
+	void backward_backward_input(hipStream_t st, const ModuleCtx* ctx, uint32_t n, const float* dL_ddLdin, const float* in,
+	                             const void* dL_dout, void* dL_dparams, void* dL_ddLdout, float* dL_din, const void* params) override {
 		const GridEncodingHost* grid = enc.lone_grid();
-		if (!grid) return ModuleBase::backward_backward_input(st, n, dL_ddLdin, in, dL_dout, dL_dparams, dL_ddLdout, dL_din, params);
+		if (!grid) return ModuleBase::backward_backward_input(st, ctx, n, dL_ddLdin, in, dL_dout, dL_dparams, dL_ddLdout, dL_din, params);
 		if (!dL_ddLdout && !dL_dparams) return;  // grid.h:913-915
 		TCNN_CHECK(params, "backward_backward_input needs the grid parameters");
 		const uint32_t W = enc.padded_output_width();
@@ -559,7 +574,7 @@ int tcnn_module_backward_backward_input(tcnn_module* m, void* stream, const tcnn
 			if (dL_dparams) TCNN_HIP_CHECK(hipMemsetAsync(dL_dparams, 0, m->m->n_params() * m->m->elem_bytes(), (hipStream_t)stream));
 			return;
 		}
-		m->m->backward_backward_input((hipStream_t)stream, n, dL_ddLdin, in, dL_dout, dL_dparams, dL_ddLdout, dL_din, params);
+		m->m->backward_backward_input((hipStream_t)stream, ctx->impl.get(), n, dL_ddLdin, in, dL_dout, dL_dparams, dL_ddLdout, dL_din, params);
 	});
 }
 

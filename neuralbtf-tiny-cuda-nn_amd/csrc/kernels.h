@@ -432,6 +432,22 @@ uint32_t f32_wgrad_slab_rows(uint32_t B);
 uint32_t f32_wgrad_n_slabs(uint32_t B);
 void launch_f32_wgrad(hipStream_t st, uint32_t B, uint32_t N, uint32_t K, const float* dy, const float* yv, int act, const float* x,
                       float* partial);
+// The second-order input gradient (NetworkF32Host::backward_backward_input). An activation has curvature when
+// act'' is not identically zero: None, ReLU and LeakyReLU have none.
+inline bool f32_act_has_curvature(int act) {
+	return act == ACT_EXPONENTIAL || act == ACT_SIGMOID || act == ACT_SQUAREPLUS || act == ACT_SOFTPLUS || act == ACT_TANH;
+}
+// tangent layer: with t = x[B][K] w^T, y[B][N] = t o act'(yv) and, when r is given (an activation with curvature),
+// r[B][N] = t o d o act''(yv); yv: the layer's forward value, d: dL/d(that value) of the first-order backward
+void launch_f32_layer_tangent(hipStream_t st, uint32_t B, uint32_t N, uint32_t K, const float* w, const float* x, const float* yv, int act,
+                              float* y, const float* d, float* r);
+// curvature layer: q_below[B][K] = (q[B][N] w) o act'(yv_below) + r_below (r_below nullable; q_below may be r_below)
+void launch_f32_layer_curvature(hipStream_t st, uint32_t B, uint32_t N, uint32_t K, const float* w, const float* q, const float* yv_below,
+                                int act_below, const float* r_below, float* q_below);
+// Identity in front: u0[B][width] = scale * u_x[B][D] in the first D columns, 0 in the padding
+void launch_f32_identity_tangent(hipStream_t st, uint32_t B, uint32_t D, uint32_t width, float scale, const float* u_x, float* u0);
+// dst[i] += src[i], i < n
+void launch_f32_add(hipStream_t st, size_t n, float* dst, const float* src);
 
 void launch_probe_hfma(hipStream_t st, const void* a, const void* b, const void* c, void* out, uint32_t n_pairs);
 // Diagnostic: the config_hash fused (pipelined) kernel with s_memtime phase stamps (prof: [blocks*8][8] u64).

@@ -1363,6 +1363,119 @@ void NetworkF32Host::backward(hipStream_t st, uint32_t B, const float* pos, cons
 	if (dL_dparams && enc->n_params() > 0) enc->backward_params(st, B, pos, dnext, 2, dL_dparams + n_mlp);
 }
 
+void NetworkF32Host::check_second_order() const {
+	TCNN_CHECK(!has_sine(), "Sine has no backward from its forward value: the MI355X engine serves it through inference only");
+	const EncodingHost::Part* lone = enc->lone_part();
+	if (!lone || (lone->kind != COMP_IDENTITY && lone->kind != COMP_GRID))
+		throw std::runtime_error("NetworkWithInputEncoding<float>::backward_backward_input behind " + enc->name() +
+		                         ": not implemented error (Identity or a grid standing alone only)");
+}
+
+// Second order ("Second-order input gradients of fp32 network modules"). Layer j = 0..NH maps h_j (width
+// K_j) to h_{j+1} = a_j(W_j h_j) (width N_j); D_j = dL/dh_j is the first-order delta, U_j = dL2/dD_j the tangent,
+// R_j = T_j o D_{j+1} o a_j''(h_{j+1}) the curvature source and Q_j = dL2/d(pre-activation of layer j).
+void NetworkF32Host::backward_backward_input(hipStream_t st, uint32_t B, const float* pos, const float* params, const float* dL_ddLdinput,
+                                             const float* dout32, const float* keep, float* dL_dparams, float* dL_ddLdoutput,
+                                             float* dL_dinput) {
+	check_second_order();
+	const EncodingHost::Part* lone = enc->lone_part();
+	const GridEncodingHost* grid = enc->lone_grid();
+	const bool identity = !grid;
+	if (!dL_dparams && !dL_ddLdoutput && !dL_dinput) return;
+	const bool need_d = dL_dparams || dL_dinput;  // everything but the tangent pass reads the first-order deltas
+	TCNN_CHECK(dout32 || !need_d, "backward_backward_input: dL_dparams and dL_dinput need dL_doutput");
+	TCNN_CHECK(dL_ddLdinput, "backward_backward_input: dL_ddLdinput is missing");
+	const uint32_t W = mlp.width, IN = mlp.n_input, NH = mlp.n_hidden_layers, OUTP = mlp.padded_output;
+	const uint32_t n_mlp = mlp.n_params(), n_enc = enc->n_params(), D = n_input_dims;
+	const float* eparams = params + n_mlp;
+	auto a = [&](uint32_t j) { return j < NH ? mlp.activation : mlp.output_activation; };
+	auto Nj = [&](uint32_t j) { return j < NH ? W : OUTP; };
+	auto Kj = [&](uint32_t j) { return j == 0 ? IN : W; };
+	auto w_off = [&](uint32_t j) -> size_t { return j == 0 ? 0 : (size_t)W * IN + (size_t)(j - 1) * W * W; };
+	// h_0 .. h_{NH+1} of the keep, and the same offsets for the chains kept here
+	auto chain = [&](uint32_t j) -> size_t { return j == 0 ? 0 : (size_t)B * IN + (size_t)(j - 1) * B * W; };
+	const size_t n_chain = chain(NH + 1), n_out = (size_t)B * OUTP;
+	// [D_0 .. D_NH | U_0 .. U_NH | U_{NH+1} | R_0 .. R_NH (Q_j in place) | P_0 | dx of P_0]
+	second.reserve((2 * n_chain + n_out + ((size_t)NH * B * W + n_out) + (size_t)B * IN + (size_t)B * D) * 4);
+	float* Dc = second.as<float>();
+	float* Uc = Dc + n_chain;
+	float* Uout = Uc + n_chain;
+	float* Rc = Uout + n_out;
+	float* P0 = Rc + (size_t)NH * B * W + n_out;
+	float* dx_tmp = P0 + (size_t)B * IN;
+	auto hv = [&](uint32_t j) { return keep + chain(j); };
+	auto Dv = [&](uint32_t j) -> const float* { return j == NH + 1 ? dout32 : Dc + chain(j); };
+	auto Rv = [&](uint32_t j) { return Rc + (size_t)j * B * W; };
+
+	// the first-order delta chain again (the forward context does not hold it); D_0 only a grid reads
+	if (need_d)
+		for (uint32_t j = NH + 1; j-- > (grid ? 0u : 1u);)
+			launch_f32_layer_bwd(st, B, Nj(j), Kj(j), params + w_off(j), Dv(j + 1), hv(j + 1), a(j), Dc + chain(j));
+
+	// 1: the encoding. U_0 = dL2/dD_0; a grid also gives its own dL2/dtable (atomic adds onto zeros) and dL2/dx
+	if (grid) {
+		if (dL_dparams) TCNN_HIP_CHECK(hipMemsetAsync(dL_dparams + n_mlp, 0, (size_t)n_enc * 4, st));
+		grid->backward_backward_input(st, B, pos, enc->n_dims, eparams, dL_ddLdinput, need_d ? Dv(0) : nullptr, IN,
+		                              dL_dparams ? dL_dparams + n_mlp : nullptr, Uc, IN, dL_dinput);
+	} else {
+		launch_f32_identity_tangent(st, B, lone->n_in, IN, lone->f0, dL_ddLdinput, Uc);
+	}
+
+	// 2: the tangent pass, bottom up; a layer with curvature leaves R_j beside U_{j+1}
+	int top = -1;  // the highest layer with curvature: Q_j = 0 above it
+	for (uint32_t j = 0; j <= NH; ++j) {
+		float* r = need_d && f32_act_has_curvature(a(j)) ? Rv(j) : nullptr;
+		if (r) top = (int)j;
+		if (j == NH && !dL_ddLdoutput && !r) break;
+		float* y = j < NH ? Uc + chain(j + 1) : dL_ddLdoutput ? dL_ddLdoutput : Uout;
+		launch_f32_layer_tangent(st, B, Nj(j), Kj(j), params + w_off(j), Uc + chain(j), hv(j + 1), a(j), y, r ? Dv(j + 1) : nullptr, r);
+	}
+	if (!need_d) return;
+
+	// 3: the curvature pass, top down, with both weight-gradient terms of a matrix in one fixed-order sum:
+	// A = sum_b (D_{j+1} o a_j'(h_{j+1})) U_j^T in slabs [0, nsl), B = sum_b Q_j h_j^T in slabs [nsl, 2 nsl)
+	const uint32_t nsl = f32_wgrad_n_slabs(B);
+	if (dL_dparams) wgrad_partial.reserve((size_t)2 * nsl * std::max(W, OUTP) * std::max(W, IN) * 4);
+	for (uint32_t j = NH + 1; j-- > 0;) {
+		const uint32_t N = Nj(j), K = Kj(j);
+		const bool have_q = (int)j <= top;
+		if (dL_dparams) {
+			float* part = wgrad_partial.as<float>();
+			launch_f32_wgrad(st, B, N, K, Dv(j + 1), hv(j + 1), a(j), Uc + chain(j), part);
+			if (have_q) launch_f32_wgrad(st, B, N, K, Rv(j), nullptr, ACT_NONE, hv(j), part + (size_t)nsl * N * K);
+			const uint32_t n_parts = have_q ? 2 * nsl : nsl;
+			const size_t tf = reduce_partials_tmp_floats(n_parts, N * K);
+			if (tf) red_tmp.reserve(tf * 4);
+			launch_reduce_partials(st, part, n_parts, N * K, N * K, dL_dparams + w_off(j), red_tmp.as<float>());
+		}
+		if (!have_q) continue;
+		if (j > 0) {  // Q_{j-1} = R_{j-1} + (Q_j W_j) o a_{j-1}'(h_j), in R_{j-1}'s place
+			const bool r_below = f32_act_has_curvature(a(j - 1));
+			launch_f32_layer_curvature(st, B, N, K, params + w_off(j), Rv(j), hv(j), a(j - 1), r_below ? Rv(j - 1) : nullptr, Rv(j - 1));
+		} else if (dL_dinput || (dL_dparams && n_enc)) {  // P_0 = Q_0 W_0 = dL2/d(encoded row)
+			launch_f32_layer_bwd(st, B, N, K, params, Rv(0), nullptr, ACT_NONE, P0);
+		}
+	}
+	// P_0 through the encoding's first-order backward, added to the grid's own terms
+	if (top < 0) {
+		if (identity && dL_dinput) TCNN_HIP_CHECK(hipMemsetAsync(dL_dinput, 0, (size_t)B * D * 4, st));
+		return;
+	}
+	if (identity) {
+		if (dL_dinput) enc->backward_input(st, B, pos, P0, dL_dinput, eparams, 2);
+		return;
+	}
+	if (dL_dinput) {
+		enc->backward_input(st, B, pos, P0, dx_tmp, eparams, 2);
+		launch_f32_add(st, (size_t)B * D, dL_dinput, dx_tmp);
+	}
+	if (dL_dparams) {
+		grid_tmp.reserve((size_t)n_enc * 4);
+		enc->backward_params(st, B, pos, P0, 2, grid_tmp.as<float>());
+		launch_f32_add(st, n_enc, dL_dparams + n_mlp, grid_tmp.as<float>());
+	}
+}
+
 // ------------------------------------------------------------------------------------------
 // Trainer (reference trainer.h:47-361, config.h:46-63)
 // ------------------------------------------------------------------------------------------

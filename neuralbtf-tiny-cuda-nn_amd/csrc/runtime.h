@@ -519,6 +519,15 @@ struct NetworkF32Host {
 	// from a forward's keep: dL/dparams fp32 [n_params()] (nullable), dL/dinput fp32 [B][n_input_dims] (nullable)
 	void backward(hipStream_t st, uint32_t B, const float* pos, const float* params, const float* dout32, const float* keep,
 	              float* dL_dparams, float* dL_dinput);
+	// Second order with respect to the input, from a forward's keep: dL_ddLdinput = dL2/d(dL/dinput) fp32
+	// [B][n_input_dims] -> dL2/dparams [n_params()], dL2/d(dL/doutput) [B][padded_output], dL2/dinput
+	// [B][n_input_dims] (each nullable, each overwritten). dout32, the first-order dL/doutput, may be null when only
+	// dL_ddLdoutput is asked for. The encoding in front is Identity or a lone grid; any other throws. The network's part
+	// of dL2/dparams is bit-reproducible, the grid's (fp32 atomics) is not.
+	void backward_backward_input(hipStream_t st, uint32_t B, const float* pos, const float* params, const float* dL_ddLdinput,
+	                             const float* dout32, const float* keep, float* dL_dparams, float* dL_ddLdoutput, float* dL_dinput);
+	void check_second_order() const;  // throws for Sine and for an encoding that is neither Identity nor a lone grid
+	DevBuf second, grid_tmp;  // grow-only scratch of backward_backward_input: its delta / tangent / curvature chains; a grid's second table gradient
 };
 
 // One RCCL communicator of a data-parallel job (dp.cpp): rank `rank` of `nranks`, one process per
