@@ -2,6 +2,7 @@
 // codes + tcnn_last_error().
 #include "../../include/tcnn_mi355x.h"
 #include "debug_api.h"  // test-only diagnostics, not in the product header
+#include "debug_adam.h"
 #include "debug_grid_bwd.h"
 
 #include <algorithm>
@@ -755,6 +756,12 @@ int tcnn_debug_peer_loopback(tcnn_trainer* t, int nranks) {
 		t->t->dp_peer_loopback(nranks);
 	});
 }
+int tcnn_debug_adam_uniform_blocks(tcnn_trainer* t, uint32_t* n_uniform, uint32_t* n_blocks) {
+	return guard([&] {
+		if (n_blocks) *n_blocks = t->t->n_step_blocks();
+		if (n_uniform) *n_uniform = t->t->uniform_step_blocks();
+	});
+}
 int tcnn_trainer_dp_peer_abandon(tcnn_trainer* t) {
 	return guard([&] { t->t->dp_peer_abandon(); });
 }
@@ -885,9 +892,19 @@ const char* tcnn_trainer_optimizer_schedule(const tcnn_trainer* t) { return !t->
 int tcnn_trainer_set_learning_rate(tcnn_trainer* t, float learning_rate) {
 	return guard([&] { t->t->set_learning_rate(learning_rate); });
 }
-void* tcnn_trainer_param_gradients(tcnn_trainer* t) { return t->t->g16.p; }
-float* tcnn_trainer_gradients_fp32(tcnn_trainer* t) { return t->t->g32.as<float>(); }
+// The raw gradient / step-count pointers may be cached by the caller: the first request makes the
+// buffers current (on the stream of the last step) and the trainer keeps them so from then on
+// (TrainerHost::lean_settle, LeanUse::Caller).
+void* tcnn_trainer_param_gradients(tcnn_trainer* t) {
+	if (guard([&] { t->t->lean_settle(TrainerHost::LeanUse::Caller); }) != 0) return nullptr;
+	return t->t->g16.p;
+}
+float* tcnn_trainer_gradients_fp32(tcnn_trainer* t) {
+	if (guard([&] { t->t->lean_settle(TrainerHost::LeanUse::Caller); }) != 0) return nullptr;
+	return t->t->g32.as<float>();
+}
 int tcnn_trainer_optimizer_state(tcnn_trainer* t, float** m1, float** m2, uint32_t** steps) {
+	if (int rc = guard([&] { t->t->lean_settle(TrainerHost::LeanUse::Caller); })) return rc;
 	if (m1) *m1 = t->t->m1.as<float>();
 	if (m2) *m2 = t->t->m2.as<float>();
 	if (steps) *steps = t->t->steps.as<uint32_t>();

@@ -123,6 +123,8 @@ void TrainerHost::set_dp(DpComm* c, bool sharded) {
 	// state under it: refused, detach the peer exchange first
 	TCNN_CHECK(!peer_attached, "set_dp: the trainer is attached to a peer exchange (detach it first)");
 	if (dp && dp_sharded && dp_state_partial) dp_gather_state(nullptr);
+	// the exchange moves g32 and steps[] (and reallocates them): eager stores and per-parameter counts from here on
+	lean_settle(c ? LeanUse::Caller : LeanUse::Write);
 	TCNN_HIP_CHECK(hipDeviceSynchronize());
 	dp = c;
 	dp_sharded = c && sharded;
@@ -200,6 +202,7 @@ void TrainerHost::dp_gather_state(hipStream_t st) {
 		return;
 	}
 	if (!dp || !dp_sharded || !dp_state_partial) return;
+	lean_settle(LeanUse::Write);
 	for (DevBuf* b : {&w32, &m1, &m2, &steps}) dp->all_gather(b->p, (size_t)dp_per, 4, st);
 	TCNN_HIP_CHECK(hipStreamSynchronize(st));
 	dp_state_partial = false;

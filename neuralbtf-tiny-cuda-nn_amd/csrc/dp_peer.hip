@@ -363,6 +363,8 @@ void TrainerHost::dp_peer_export(int nranks, int rank, void* blob_out) {
 	TCNN_CHECK(nranks >= 1 && rank >= 0 && rank < nranks, "peer exchange: rank outside [0, nranks)");
 	TCNN_CHECK(nranks <= PEER_MAX_RANKS, "peer exchange: at most 64 ranks (the ranks of one node)");
 	if (peer) dp_peer_detach();
+	// the peers read g32 and the state arrays (reallocated below): eager stores and per-parameter counts from here on
+	lean_settle(LeanUse::Caller);
 	TCNN_HIP_CHECK(hipDeviceSynchronize());
 	auto pd = std::make_shared<PeerDp>();
 	pd->nranks = nranks;

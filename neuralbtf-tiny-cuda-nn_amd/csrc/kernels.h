@@ -104,7 +104,21 @@ struct AdamArgs {
 	uint32_t factor_n;
 	// grid slabs: parameter i reads slab element grid_slab_index(part_map, i - begin) (nullptr: i - begin)
 	const GridSlabMap* part_map;
+	// Slab-summing launches only (part != nullptr), EngineSwitches::adam_lean:
+	// ADAM_LEAN_GRADS: grad32[i] and grad16[i] are not stored (the slabs stay intact after the step; the
+	// trainer sums them again when a caller asks for the gradients).
+	// ADAM_LEAN_STEPS: step_blocks[b] is the common step count of parameters [begin + 256 b, begin + 256 b +
+	// 256) and steps[] is neither read nor written for them, or ADAM_STEPS_DIVERGED: steps[] is
+	// authoritative. After every launch a block's word is a count exactly when its counts are all equal.
+	uint32_t lean;
+	uint32_t* step_blocks;
 };
+
+// Default: the gradient stores only. The block counts measured slower at 2^18 (k_adam 11.2 against 10.2 us): a
+// block that once diverged stays so, and after 220 bench steps 3 of 2768 blocks were still uniform (DESIGN (f) 5).
+enum : uint32_t { ADAM_LEAN_GRADS = 1u, ADAM_LEAN_STEPS = 2u, ADAM_LEAN_ALL = 3u, ADAM_LEAN_DEFAULT = ADAM_LEAN_GRADS };
+constexpr uint32_t ADAM_STEPS_DIVERGED = 0xFFFFFFFFu;
+constexpr uint32_t ADAM_STEP_BLOCK = 256;
 
 // Optimizer state buffers (full parameter vector [network | encoding]).
 struct AdamBuffers {
@@ -318,6 +332,12 @@ void launch_generate_logistic(hipStream_t st, uint64_t n, uint64_t state, uint64
 void launch_add_perturbation(hipStream_t st, uint32_t n, const void* out16, const float* noise, void* pert16);
 void launch_adam(hipStream_t st, const AdamArgs& a, float* w32, void* w16, const float* grad32, void* grad16,
                  float* m1, float* m2, uint32_t* steps);
+// What a lean launch_adam (ADAM_LEAN_GRADS) left out, from the slabs it summed: grad32[p] = the fixed-order
+// slab sum, grad16[p] = f16_rn(sum * grad_scale), p < n -- the values and bits k_adam stores.
+void launch_grid_slab_gradients(hipStream_t st, const float* in, uint32_t n_parts, uint32_t stride, uint32_t n, const GridSlabMap* map,
+                                float grad_scale, float* grad32, void* grad16);
+// steps[256 b + k] = step_blocks[b] for every block b < n_blocks whose word is a count (k < 256, 256 b + k < n)
+void launch_adam_steps_expand(hipStream_t st, const uint32_t* step_blocks, uint32_t n, uint32_t* steps);
 
 void launch_cast_f32_f16(hipStream_t st, const float* in, void* out, size_t n);
 void launch_cast_f16_f32(hipStream_t st, const void* in, float* out, size_t n);

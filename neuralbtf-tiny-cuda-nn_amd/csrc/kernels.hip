@@ -194,21 +194,86 @@ void launch_generate_uniform(hipStream_t st, uint64_t n, uint64_t state, uint64_
 
 
 // reference optimizers/adam.h:47-119 (per-parameter update in adam_device.h)
+// LEAN = 0: every launch that reads grad32, and the slab-summing launch that stores all it computes.
+// LEAN != 0 (slab-summing launches only): the AdamArgs::lean bits -- ADAM_LEAN_GRADS leaves the
+// gradient stores out, ADAM_LEAN_STEPS keeps one step count per 256-parameter workgroup while the
+// workgroup's parameters agree on it. The arithmetic per parameter is adam_core's in every variant.
+template <uint32_t LEAN>
 __global__ __launch_bounds__(256) void k_adam(const AdamArgs a, float* __restrict__ w32, _Float16* __restrict__ w16,
                                                const float* __restrict__ grad32, _Float16* __restrict__ grad16,
                                                float* __restrict__ m1, float* __restrict__ m2, uint32_t* __restrict__ steps) {
+	static_assert(ADAM_STEP_BLOCK == 256, "one step-count word per workgroup");
 	const uint32_t i = a.begin + blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= a.n) return;
-	float gsum;
-	if (a.part) {
-		const uint32_t q = a.part_map ? grid_slab_index(a.part_map, i - a.begin) : i - a.begin;
-		gsum = slab_sum(a.part + q, a.part_stride, a.n_parts);
-		((float*)grad32)[i] = gsum;
+	if constexpr (LEAN == 0) {
+		if (i >= a.n) return;
+		float gsum;
+		if (a.part) {
+			const uint32_t q = a.part_map ? grid_slab_index(a.part_map, i - a.begin) : i - a.begin;
+			gsum = slab_sum(a.part + q, a.part_stride, a.n_parts);
+			((float*)grad32)[i] = gsum;
+		} else {
+			gsum = grad32[i];
+		}
+		const AdamBuffers s{w32, w16, (float*)grad32, grad16, m1, m2, steps};
+		adam_update(a, s, i, gsum);
 	} else {
-		gsum = grad32[i];
+		constexpr bool GRADS = (LEAN & ADAM_LEAN_GRADS) == 0, BLOCKS = (LEAN & ADAM_LEAN_STEPS) != 0;
+		// threads past a.n stay for the workgroup's vote and agree with everything
+		const bool live = i < a.n;
+		if (!BLOCKS && !live) return;
+		// the block word first, then every load that does not depend on it
+		uint32_t word = ADAM_STEPS_DIVERGED;
+		if (BLOCKS) word = a.step_blocks[blockIdx.x];
+		float gsum = 0.0f, w = 0.0f, mo1 = 0.0f, mo2 = 0.0f;
+		if (live) {
+			const uint32_t q = a.part_map ? grid_slab_index(a.part_map, i - a.begin) : i - a.begin;
+			gsum = slab_sum(a.part + q, a.part_stride, a.n_parts);
+			w = w32[i];
+			mo1 = m1[i];
+			mo2 = m2[i];
+		}
+		const bool uniform = word != ADAM_STEPS_DIVERGED;  // the same for the whole workgroup
+		uint32_t step = uniform ? word : (live ? steps[i] : 0u);
+		bool upd = false;
+		if (live) {
+			_Float16 g16;
+			upd = adam_core(a, i, gsum, g16, w, mo1, mo2, step);
+			if (GRADS) {
+				((float*)grad32)[i] = gsum;
+				if (grad16) grad16[i] = g16;
+			}
+			if (upd) {
+				w32[i] = w;
+				m1[i] = mo1;
+				m2[i] = mo2;
+				w16[i] = f16_rn(w);
+			}
+		}
+		if (!BLOCKS) {
+			if (upd) steps[i] = step;
+			return;
+		}
+		if (uniform) {
+			// all updated: the common count moves on; none: nothing changes; mixed: the counts part ways
+			const uint32_t n_live = min(ADAM_STEP_BLOCK, a.n - (a.begin + blockIdx.x * ADAM_STEP_BLOCK));
+			const uint32_t n_upd = (uint32_t)__syncthreads_count(upd ? 1 : 0);
+			if (n_upd == n_live) {
+				if (threadIdx.x == 0) a.step_blocks[blockIdx.x] = word + 1u;
+			} else if (n_upd != 0) {
+				if (live) steps[i] = step;
+				if (threadIdx.x == 0) a.step_blocks[blockIdx.x] = ADAM_STEPS_DIVERGED;
+			}
+		} else {
+			// today's per-parameter counts; the workgroup becomes uniform again once they all agree
+			if (upd) steps[i] = step;
+			__shared__ uint32_t first;
+			if (threadIdx.x == 0) first = step;  // thread 0 of a launched workgroup is always live
+			__syncthreads();
+			const uint32_t f = first;
+			const int same = __syncthreads_and((!live || step == f) ? 1 : 0);
+			if (same && threadIdx.x == 0 && f != ADAM_STEPS_DIVERGED) a.step_blocks[blockIdx.x] = f;
+		}
 	}
-	const AdamBuffers s{w32, w16, (float*)grad32, grad16, m1, m2, steps};
-	adam_update(a, s, i, gsum);
 }
 
 void launch_adam(hipStream_t st, const AdamArgs& a, float* w32, void* w16, const float* grad32, void* grad16,
@@ -217,7 +282,48 @@ void launch_adam(hipStream_t st, const AdamArgs& a, float* w32, void* w16, const
 	// one parameter per thread: measured faster than 4-wide vector access (16.7 vs 19.5 us for the
 	// config_hash grid range with 8 slabs) -- 4x the waves in flight for the slab loads; r06 again with
 	// the slabs in parameter order (16-byte slab and state loads): 9.3 vs 8.7 us at 2^15, 13.5 vs 13.0 at 2^18
-	hipLaunchKernelGGL(k_adam, dim3(div_round_up(a.n - a.begin, 256)), dim3(256), 0, st, a, w32, (_Float16*)w16, grad32, (_Float16*)grad16, m1, m2, steps);
+	const dim3 grid(div_round_up(a.n - a.begin, ADAM_STEP_BLOCK));
+	const uint32_t lean = a.part ? (a.lean & ADAM_LEAN_ALL) : 0u;
+	TCNN_CHECK(!(lean & ADAM_LEAN_STEPS) || a.step_blocks, "launch_adam: block step counts without their buffer");
+#define TCNN_LAUNCH_ADAM(L) \
+	hipLaunchKernelGGL(k_adam<L>, grid, dim3(256), 0, st, a, w32, (_Float16*)w16, grad32, (_Float16*)grad16, m1, m2, steps)
+	switch (lean) {
+		case 0: TCNN_LAUNCH_ADAM(0u); break;
+		case 1: TCNN_LAUNCH_ADAM(1u); break;
+		case 2: TCNN_LAUNCH_ADAM(2u); break;
+		default: TCNN_LAUNCH_ADAM(3u); break;
+	}
+#undef TCNN_LAUNCH_ADAM
+	TCNN_HIP_CHECK(hipGetLastError());
+}
+
+__global__ __launch_bounds__(256) void k_grid_slab_gradients(const float* __restrict__ in, uint32_t n_parts, uint32_t stride, uint32_t n,
+                                                              const GridSlabMap* __restrict__ map, float grad_scale,
+                                                              float* __restrict__ grad32, _Float16* __restrict__ grad16) {
+	const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+	if (p >= n) return;
+	const float s = slab_sum(in + (map ? grid_slab_index(map, p) : p), stride, n_parts);
+	grad32[p] = s;
+	grad16[p] = f16_rn(s * grad_scale);
+}
+
+void launch_grid_slab_gradients(hipStream_t st, const float* in, uint32_t n_parts, uint32_t stride, uint32_t n, const GridSlabMap* map,
+                                float grad_scale, float* grad32, void* grad16) {
+	if (!n) return;
+	hipLaunchKernelGGL(k_grid_slab_gradients, dim3(div_round_up(n, 256)), dim3(256), 0, st, in, n_parts, stride, n, map, grad_scale, grad32,
+	                   (_Float16*)grad16);
+	TCNN_HIP_CHECK(hipGetLastError());
+}
+
+__global__ __launch_bounds__(256) void k_adam_steps_expand(const uint32_t* __restrict__ step_blocks, uint32_t n, uint32_t* __restrict__ steps) {
+	const uint32_t word = step_blocks[blockIdx.x];
+	const uint32_t i = blockIdx.x * ADAM_STEP_BLOCK + threadIdx.x;
+	if (word != ADAM_STEPS_DIVERGED && i < n) steps[i] = word;
+}
+
+void launch_adam_steps_expand(hipStream_t st, const uint32_t* step_blocks, uint32_t n, uint32_t* steps) {
+	if (!n) return;
+	hipLaunchKernelGGL(k_adam_steps_expand, dim3(div_round_up(n, ADAM_STEP_BLOCK)), dim3(256), 0, st, step_blocks, n, steps);
 	TCNN_HIP_CHECK(hipGetLastError());
 }
 

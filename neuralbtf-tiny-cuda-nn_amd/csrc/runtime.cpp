@@ -109,6 +109,7 @@ EngineSwitches EngineSwitches::from_env() {
 		if (std::atoi(e) > 0) s.grid_bwd_ranges = (uint32_t)std::atoi(e);
 	if (const char* e = std::getenv("TCNN_GRID_BWD_STREAM")) s.no_grid_bwd_stream = std::string(e) == "0";
 	if (const char* e = std::getenv("TCNN_WT_STORES")) s.wt_stores = (uint32_t)std::strtoul(e, nullptr, 0) & WT_STORES_ALL;
+	if (const char* e = std::getenv("TCNN_ADAM_LEAN")) s.adam_lean = (uint32_t)std::strtoul(e, nullptr, 0) & ADAM_LEAN_ALL;
 	if (const char* e = std::getenv("TCNN_GRID_BWD_PLAN")) s.grid_bwd_plan = std::string(e) == "feature" ? 1 : (std::string(e) == "range" ? 0 : -1);
 	return s;
 }
@@ -1534,6 +1535,13 @@ void TrainerHost::initialize_params_rng(Pcg32& rng) {
 	TCNN_HIP_CHECK(hipMemset(m2.p, 0, n_params * 4));
 	TCNN_HIP_CHECK(hipMemset(steps.p, 0, n_params * 4));
 	TCNN_HIP_CHECK(hipMemset(d_loss.p, 0, 16));
+	if (n_step_blocks()) {  // every block uniform at count 0, like steps[]
+		step_blocks.reserve((size_t)n_step_blocks() * 4);
+		TCNN_HIP_CHECK(hipMemset(step_blocks.p, 0, (size_t)n_step_blocks() * 4));
+	}
+	grads_stale = false;
+	steps_current = true;
+	step_blocks_diverged = false;
 	launch_cast_f32_f16(nullptr, w32.as<float>(), w16.p, n_params);
 	TCNN_HIP_CHECK(hipDeviceSynchronize());
 	adam_step = 0;
@@ -1557,6 +1565,9 @@ void TrainerHost::set_params_full_precision(const float* host, uint64_t n) {
 
 void TrainerHost::training_step(hipStream_t st, uint32_t B, const float* input, const float* target, bool run_optimizer) {
 	TCNN_CHECK(B % BATCH_GRANULARITY == 0, "training_step: batch size must be a multiple of 256");
+	// only the one-call step carries lean state on; every other schedule reads or overwrites g32 / g16 /
+	// steps[] / the slabs
+	if (!(run_optimizer && lean_mask() != 0)) lean_settle(LeanUse::Write);
 	if (timer.enabled) {
 		timer.sampling = (timer.counter++ % timer.every) == 0;
 		if (timer.sampling) timer.marks.push_back({-1, -1, -1, -1, -1});
@@ -1662,8 +1673,14 @@ void TrainerHost::training_step_overlapped(hipStream_t st, uint32_t B, const flo
 		ag.n_parts = ws.gbw.n_chunks;
 		ag.part_stride = g.n_lds_params;
 		ag.part_map = g.slab_map(ws.gbw.plan);
+		// nothing in the step reads the grid range of g32 / g16, and blocks of parameters that were all
+		// hit share one step count: both are settled when somebody asks (lean_settle)
+		ag.lean = lean_mask();
+		ag.step_blocks = step_blocks.as<uint32_t>();
+		TCNN_CHECK(steps_current || (ag.lean & ADAM_LEAN_STEPS), "training step: block step counts were not expanded");
 		if (!g.plans[0].slices.empty())
 			launch_adam(st, ag, w32.as<float>(), w16.p, g32.as<float>(), g16.p, m1.as<float>(), m2.as<float>(), steps.as<uint32_t>());
+		lean_note_step(st, ag.lean);
 	} else {
 		g.backward_acc(st, ws.gbw, B, ws.dLdenc.p, 0, 0, gsum + n_mlp);
 		timer.mark(st, 2);
@@ -1728,7 +1745,9 @@ std::vector<uint64_t> TrainerHost::graph_key(uint32_t B, const float* input, con
 	                           (uint64_t)(uintptr_t)ws.enc16.p, (uint64_t)(uintptr_t)ws.acts.p, (uint64_t)(uintptr_t)ws.delta0.p,
 	                           (uint64_t)(uintptr_t)ws.delta1.p, (uint64_t)(uintptr_t)ws.dout16.p, (uint64_t)(uintptr_t)ws.out16.p,
 	                           (uint64_t)(uintptr_t)ws.red_tmp.p, (uint64_t)(uintptr_t)ws.tile_wT.p, (uint64_t)(uintptr_t)ws.loss_sum.p,
-	                           ws.n_loss_partials, (uint64_t)(uintptr_t)peer.get(), (uint64_t)peer_attached};
+	                           ws.n_loss_partials, (uint64_t)(uintptr_t)peer.get(), (uint64_t)peer_attached,
+	                           // which k_adam variant the capture holds (the sticky switches re-capture)
+	                           (uint64_t)lean_mask(), (uint64_t)(uintptr_t)step_blocks.p};
 	// every scalar the step's kernels take from the trainer (AdamArgs holds no pointer here)
 	const AdamArgs a = adam_args();
 	const size_t n = sizeof(AdamArgs) / 8 + 1;
@@ -1768,6 +1787,9 @@ bool TrainerHost::training_step_graph(hipStream_t st, uint32_t B, const float* i
 		}
 		const uint32_t step0 = adam_step, ftv0 = ftable_valid, lb0 = last_B;
 		const bool wv0 = ws.wimage_valid, dps0 = dp_state_partial;
+		const bool gst0 = grads_stale, sc0 = steps_current, sbd0 = step_blocks_diverged;
+		const float sgs0 = stale_grad_scale;
+		hipStream_t const lst0 = lean_st;
 		hipGraph_t g = nullptr;
 		const bool tim = timer.enabled;
 		timer.enabled = false;  // no phase events inside the graph
@@ -1780,6 +1802,11 @@ bool TrainerHost::training_step_graph(hipStream_t st, uint32_t B, const float* i
 		last_B = lb0;
 		ws.wimage_valid = wv0;
 		dp_state_partial = dps0;
+		grads_stale = gst0;
+		steps_current = sc0;
+		step_blocks_diverged = sbd0;
+		stale_grad_scale = sgs0;
+		lean_st = lst0;
 		hipGraphExec_t e = nullptr;
 		const hipError_t err = hipGraphInstantiate(&e, g, nullptr, nullptr, 0);
 		(void)hipGraphDestroy(g);
@@ -1795,6 +1822,7 @@ bool TrainerHost::training_step_graph(hipStream_t st, uint32_t B, const float* i
 	++adam_step;
 	ws.wimage_valid = image_step;  // the data-parallel steps leave the weight image to be rebuilt by the next step
 	if ((dp && dp_sharded) || peer_attached) dp_state_partial = true;
+	if (image_step) lean_note_step(st, lean_mask());  // the captured k_adam is the key's variant
 	last_B = B;
 	++graph_replays;
 	return true;
@@ -1875,6 +1903,7 @@ AdamArgs TrainerHost::adam_args() const {
 void TrainerHost::training_step_part(hipStream_t st, uint32_t B, const float* input, const float* target, int part) {
 	TCNN_CHECK(B % BATCH_GRANULARITY == 0, "training_step: batch size must be a multiple of 256");
 	TCNN_CHECK(part == 0 || part == 1, "training_step_part: part must be 0 or 1");
+	lean_settle(LeanUse::Write);
 	if (!overlapped_ok()) {
 		if (part == 0) training_step(st, B, input, target, false);
 		return;
@@ -1931,6 +1960,7 @@ AdamArgs TrainerHost::adam_args_table(hipStream_t st, uint32_t upto, uint32_t re
 }
 
 void TrainerHost::optimizer_step(hipStream_t st) {
+	lean_settle(LeanUse::Write);  // the gradients of a one-call step, and per-parameter counts for adam_apply
 	if (opt) {  // the tree on the gradient buffers: the fp16 gradients first (Adam's own rounding of the sums)
 		launch_grad_f16(st, g32.as<float>(), g16.p, grad_scale, n_params);
 		OptStep s;
@@ -1942,6 +1972,68 @@ void TrainerHost::optimizer_step(hipStream_t st) {
 		return;
 	}
 	adam_apply(st, g32.as<float>(), grad_scale, g16.p);
+}
+
+// ---- lean Adam over the grid slabs: what the one-call step leaves undone, settled on request ----
+uint32_t TrainerHost::n_step_blocks() const {
+	return model->grid ? div_round_up(model->grid->n_lds_params, ADAM_STEP_BLOCK) : 0u;
+}
+
+uint32_t TrainerHost::lean_mask() const {
+	if (opt || dp || peer_attached || !overlapped_ok() || !model->grid || model->grid->plans[0].slices.empty()) return 0;
+	uint32_t m = adam_lean;
+	if (grads_eager) m &= ~ADAM_LEAN_GRADS;
+	if (steps_per_param) m &= ~ADAM_LEAN_STEPS;
+	return m;
+}
+
+void TrainerHost::lean_note_step(hipStream_t st, uint32_t lean) {
+	lean_st = st;
+	grads_stale = (lean & ADAM_LEAN_GRADS) != 0;
+	stale_grad_scale = grad_scale;
+	if (lean & ADAM_LEAN_STEPS) {
+		steps_current = false;
+		step_blocks_diverged = false;
+	}
+}
+
+// g32 / g16 of the grid range from the last step's slabs, which nothing has overwritten since (every
+// backward settles first): plan, chunk count and slab buffer are still the step's in ws.gbw
+void TrainerHost::grads_materialize() {
+	if (!grads_stale) return;
+	const GridEncodingHost& g = *model->grid;
+	launch_grid_slab_gradients(lean_st, ws.gbw.partial.as<float>(), ws.gbw.n_chunks, g.n_lds_params, g.n_lds_params, g.slab_map(ws.gbw.plan),
+	                           stale_grad_scale, g32.as<float>() + n_mlp, g16.as<_Float16>() + n_mlp);
+	grads_stale = false;
+}
+
+void TrainerHost::steps_expand(LeanUse use) {
+	if (!n_step_blocks()) return;
+	if (!steps_current) {
+		launch_adam_steps_expand(lean_st, step_blocks.as<uint32_t>(), model->grid->n_lds_params, steps.as<uint32_t>() + n_mlp);
+		steps_current = true;
+	}
+	if (use != LeanUse::Read && !step_blocks_diverged) {
+		TCNN_HIP_CHECK(hipMemsetAsync(step_blocks.p, 0xFF, (size_t)n_step_blocks() * 4, lean_st));
+		step_blocks_diverged = true;
+	}
+}
+
+void TrainerHost::lean_settle(LeanUse use) {
+	grads_materialize();
+	steps_expand(use);
+	if (use == LeanUse::Caller) grads_eager = steps_per_param = true;
+}
+
+uint32_t TrainerHost::uniform_step_blocks() {
+	const uint32_t n = n_step_blocks();
+	if (!n) return 0;
+	std::vector<uint32_t> h(n);
+	TCNN_HIP_CHECK(hipStreamSynchronize(lean_st));
+	TCNN_HIP_CHECK(hipMemcpy(h.data(), step_blocks.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+	uint32_t u = 0;
+	for (uint32_t w : h) u += w != ADAM_STEPS_DIVERGED ? 1u : 0u;
+	return u;
 }
 
 std::unique_ptr<TrainerFwdCtx> TrainerHost::forward(hipStream_t st, uint32_t B, const float* input, const float* target, const float* pdf,
@@ -1979,6 +2071,7 @@ std::unique_ptr<TrainerFwdCtx> TrainerHost::forward(hipStream_t st, uint32_t B, 
 
 void TrainerHost::backward(hipStream_t st, const TrainerFwdCtx& c, uint32_t B, const float* input, float* dL_dinput, int gradient_mode) {
 	TCNN_CHECK(B == c.B, "backward: batch size differs from the forward's");
+	lean_settle(LeanUse::Write);  // Accumulate adds to g32; the backward overwrites the slabs
 	TCNN_CHECK(!c.inference_params,
 	           "backward: use_inference_params is honoured by inference and by a forward without a backward only; this context's "
 	           "forward read the optimizer's custom weights, and gradients are taken at the training parameters");
@@ -2014,6 +2107,7 @@ float TrainerHost::ctx_loss(hipStream_t st, const TrainerFwdCtx& c) {  // traine
 
 void TrainerHost::optimizer_step_range(hipStream_t st, uint64_t begin, uint64_t end) {
 	require_plain_adam("optimizer_step_range");
+	lean_settle(LeanUse::Write);
 	TCNN_CHECK(begin <= end && end <= n_params, "optimizer_step_range: range outside the parameter vector");
 	++adam_step;
 	AdamArgs a = adam_args_table(st, adam_step);

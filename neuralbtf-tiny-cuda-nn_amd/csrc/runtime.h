@@ -90,6 +90,11 @@ struct EngineSwitches {
 	// TCNN_WT_STORES=<mask>: the training step's hand-off stores that write through L2 (wt_store.h:
 	// WT_WGRAD_SLAB 1, WT_GRID_SLAB 2); 0: all plain (A/B). Results do not depend on it.
 	uint32_t wt_stores = WT_STORES_DEFAULT;
+	// TCNN_ADAM_LEAN=<mask>: what the trainer's Adam over the grid slabs leaves out of its traffic
+	// (kernels.h: ADAM_LEAN_GRADS 1 the gradient stores, produced when a caller asks; ADAM_LEAN_STEPS 2
+	// per-parameter step counts of blocks that agree, off by default: measured slower); 0: every store and
+	// count (A/B). Results do not depend on it.
+	uint32_t adam_lean = ADAM_LEAN_DEFAULT;
 	static EngineSwitches from_env();
 };
 
@@ -598,6 +603,40 @@ struct TrainerHost {
 	float grad_scale_user = 1.0f;  // the caller's factor (tcnn_trainer_set_gradient_scale); x 1/N under set_dp
 	float loss_scale = 128.0f;  // default_loss_scale<__half> (common.h:232)
 	uint32_t last_B = 0;
+
+	// ---- lean Adam over the grid slabs (EngineSwitches::adam_lean; k_adam<LEAN>, kernels.hip) ----
+	// The one-call single-GPU step (training_step_overlapped with the optimizer, eager or replayed) may
+	// leave two things undone in the grid range [n_mlp, n_mlp + n_lds_params); every other reader or
+	// writer of that state goes through lean_settle first.
+	//  * ADAM_LEAN_GRADS: g32 / g16 are not stored. grads_stale says so; the step's chunk slabs stay
+	//    intact in ws.gbw until the next backward, so grads_materialize() sums them again (same slab
+	//    order, same f16_rn(sum * grad_scale)) on the stream of that step.
+	//  * ADAM_LEAN_STEPS: step_blocks holds one count per 256 parameters (AdamArgs::step_blocks);
+	//    steps[] is current only for the diverged blocks until steps_expand() writes the others out.
+	// A caller who asked for the raw pointers (tcnn_trainer_param_gradients / _gradients_fp32 /
+	// _optimizer_state) may cache them, so that switches the trainer to the eager stores / per-parameter
+	// counts for good (LeanUse::Caller); so does attaching a data-parallel exchange.
+	uint32_t adam_lean = EngineSwitches::from_env().adam_lean;
+	bool grads_eager = false, steps_per_param = false;  // sticky (LeanUse::Caller)
+	bool grads_stale = false;                           // the grid range of g32 / g16 is one step behind the slabs
+	float stale_grad_scale = 1.0f;                      // grad_scale of the step whose slabs they are
+	hipStream_t lean_st = nullptr;                      // the stream of the last lean step
+	DevBuf step_blocks;                                 // uint32 [n_step_blocks()], 0 after initialize_params
+	bool steps_current = true;                          // steps[] holds every count
+	bool step_blocks_diverged = false;                  // every word is ADAM_STEPS_DIVERGED (nothing to expand or mark)
+	uint32_t n_step_blocks() const;
+	// the AdamArgs::lean bits of a one-call step taken now (0: not on that path, or all switched off)
+	uint32_t lean_mask() const;
+	// Read: g32 / g16 / steps[] are made current and stay so until the next lean step. Write: also
+	// marks every block diverged, for whoever updates steps[] itself (the next lean steps vote the
+	// blocks uniform again). Caller: Write, and the trainer stays eager / per-parameter from now on.
+	enum class LeanUse { Read, Write, Caller };
+	void lean_settle(LeanUse use);
+	void grads_materialize();
+	void steps_expand(LeanUse use);
+	void lean_note_step(hipStream_t st, uint32_t lean);  // host-side state after a one-call step (eager or replayed)
+	uint32_t uniform_step_blocks();  // debug_adam.h: blocks whose word is a count (synchronises)
+
 	// two-launch single-GPU step: reductions + Adam fused into the grid backward's epilogue
 	bool overlapped_ok() const { return model->fused_ok(); }
 	// The two schedules of a step. grad_out (run_optimizer = false only): where the fp32 gradient sums go

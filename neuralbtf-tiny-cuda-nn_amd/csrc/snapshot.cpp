@@ -266,6 +266,7 @@ std::vector<uint8_t> TrainerHost::serialize(bool with_optimizer) {
 	TCNN_CHECK(!(with_optimizer && dp_sharded && dp_state_partial),
 	           "serialize(optimizer): the sharded data-parallel optimizer state is current only on each rank's shard; "
 	           "gather it first (tcnn_trainer_dp_gather_state)");
+	lean_settle(LeanUse::Read);  // steps[] with the uniform blocks written out; the block words stay
 	TCNN_HIP_CHECK(hipDeviceSynchronize());
 	const size_t n = n_params;
 	MsgWriter w;
@@ -340,6 +341,8 @@ std::vector<uint8_t> TrainerHost::serialize(bool with_optimizer) {
 }
 
 void TrainerHost::deserialize(const void* data, size_t size) {
+	// the loaded counts land in steps[]: every block starts diverged and the next steps' votes compact them
+	lean_settle(LeanUse::Write);
 	// training steps may still be queued on the caller's (possibly non-blocking) stream
 	TCNN_HIP_CHECK(hipDeviceSynchronize());
 	MsgValue root;
