@@ -22,13 +22,13 @@ def rgb_field(pos):
     return np.stack([r, g, b], axis=1).astype(np.float32)
 
 
-def make_batch(B, seed=1337, step=0):
-    """positions [B,2] from pcg32{seed} in generate_random_uniform order (random.h:39-70),
-    advanced by `step` batches; targets from rgb_field."""
+def make_batch(B, seed=1337, step=0, n_dims=2):
+    """positions [B,n_dims] from pcg32{seed} in generate_random_uniform order (random.h:39-70),
+    advanced by `step` batches; targets from rgb_field (of the first two coordinates)."""
     r = O.pcg32(seed)
     if step:
-        O.lib().orc_pcg32_advance(ctypes.byref(r), 2 * B * step)
-    pos = O.generate_uniform(r, 2 * B).reshape(B, 2)
+        O.lib().orc_pcg32_advance(ctypes.byref(r), n_dims * B * step)
+    pos = O.generate_uniform(r, n_dims * B).reshape(B, n_dims)
     return pos, rgb_field(pos)
 
 
@@ -149,6 +149,7 @@ def assert_within_fp16_ulps(got, ref, n_ulp=4):
     ulp = float(np.spacing(np.float16(scale)))
     err = float(np.abs(np.asarray(got, np.float64) - np.asarray(ref, np.float64)).max())
     assert err <= n_ulp * ulp, (err, ulp, scale)
+    return err / ulp
 
 
 def wgrad_per_element_bound(ref, mag, ulps=8, fp16_out=False, floor_rel=1e-6):
@@ -192,7 +193,7 @@ def relu_margin_ok(W, IN, NH, params16, x_rows, tau=2.0 ** -11, check_output=Fal
         p = O.h2f(O.f2h((p * scale).astype(np.float32))).astype(np.float64)
     leaky = act.lower() == "leakyrelu"
     branchy = act.lower() in ("relu", "leakyrelu")
-    assert branchy or not check_output, "check_output needs a ReLU or LeakyReLU network: " + act
+    assert branchy or act.lower() == "none" or not check_output, "check_output needs a None, ReLU or LeakyReLU network: " + act
     assert branchy or act.lower() == "none" or out_rows == 0 or NH == 0, \
         "the hidden activation must be None, ReLU or LeakyReLU when out_rows > 0: " + act
     mats, off, k = [], 0, IN
@@ -225,15 +226,15 @@ def relu_margin_ok(W, IN, NH, params16, x_rows, tau=2.0 ** -11, check_output=Fal
     return ok
 
 
-def relu_safe_grid_batch(cfg, params16, B, seed=1337, step=0):
-    """A B-point batch (make_batch order) of samples clear of the ReLU boundaries (relu_margin_ok) for
-    the grid-encoded network of cfg at params16."""
+def relu_safe_grid_batch(cfg, params16, B, seed=1337, step=0, n_dims=2):
+    """A B-point batch (make_batch order, n_dims position columns) of samples clear of the ReLU boundaries
+    (relu_margin_ok) for the grid-encoded network of cfg at params16."""
     W, NH = cfg["network"]["n_neurons"], cfg["network"]["n_hidden_layers"]
-    g = O.grid_cfg(cfg["encoding"], 2)
+    g = O.grid_cfg(cfg["encoding"], n_dims)
     IN = g.n_levels * g.n_features_per_level
     nm = O.mlp_n_params(W, IN, NH, 16)
     p16 = np.asarray(params16, np.uint16)
-    pos, tgt = make_batch(4 * B, seed=seed, step=step)
+    pos, tgt = make_batch(4 * B, seed=seed, step=step, n_dims=n_dims)
     enc = O.h2f(O.grid_fwd(g, pos, p16[nm:])).T  # [B][IN]
     ok = relu_margin_ok(W, IN, NH, p16[:nm], enc, check_output=True)
     assert ok.sum() >= B, ok.sum()
@@ -250,15 +251,17 @@ def trainer_grad_bounds(cfg, params16, pos, tgt, n_threads=4):
     its neighbouring value moves it by up to an ulp of that magnitude, cancellation included)."""
     enc_cfg, net = cfg["encoding"], cfg["network"]
     W, NH = net["n_neurons"], net["n_hidden_layers"]
+    act = O.act_code(net.get("activation", "ReLU"))  # the hidden activation (ReLU or None: the fused kernel's two)
     g = O.grid_cfg(enc_cfg, pos.shape[1])
     IN = g.n_levels * g.n_features_per_level
     nm = O.mlp_n_params(W, IN, NH, 16)
     p16 = np.asarray(params16, np.uint16)
     enc = O.grid_fwd(g, pos, p16[nm:])
-    out16, hidden = O.mlp_fwd(W, IN, NH, 16, p16[:nm], enc, n_threads=n_threads)
+    out16, hidden = O.mlp_fwd(W, IN, NH, 16, p16[:nm], enc, activation=act, n_threads=n_threads)
     _, dout, _ = O.relative_l2(out16, tgt)
-    mag, denc_abs = O.mlp_wgrad_magnitude(W, IN, NH, 16, p16[:nm], enc, hidden, dout, n_threads=n_threads, want_dinput=True)
-    _, denc = O.mlp_bwd(W, IN, NH, 16, p16[:nm], enc, hidden, dout, n_threads=n_threads)
+    mag, denc_abs = O.mlp_wgrad_magnitude(W, IN, NH, 16, p16[:nm], enc, hidden, dout, activation=act, n_threads=n_threads,
+                                          want_dinput=True)
+    _, denc = O.mlp_bwd(W, IN, NH, 16, p16[:nm], enc, hidden, dout, activation=act, n_threads=n_threads)
     ref_grid = O.grid_bwd(g, pos, denc)
     absum, _ = O.grid_bwd_stats(g, pos, denc_abs)
     grid_bound = O.grid_grad_tolerance(g, pos, denc, ref_grid) + 8 * 2.0 ** -10 * absum.astype(np.float64)
@@ -266,8 +269,10 @@ def trainer_grad_bounds(cfg, params16, pos, tgt, n_threads=4):
 
 
 def assert_trainer_grads_per_element(g32, ref32, n_mlp, mag, grid_bound):
-    assert_wgrad_per_element(g32[:n_mlp], ref32[:n_mlp], mag)
+    """returns the worst error / bound ratios (network part, grid part)"""
+    r_mlp = assert_wgrad_per_element(g32[:n_mlp], ref32[:n_mlp], mag)
     got, ref = np.asarray(g32[n_mlp:], np.float64), np.asarray(ref32[n_mlp:], np.float64)
     r = np.abs(got - ref) / (grid_bound + 1e-30)
     k = int(np.argmax(r))
     assert r[k] <= 1.0, (float(r[k]), k, got[k], ref[k], grid_bound[k])
+    return r_mlp, float(r[k])

@@ -33,6 +33,7 @@ GRID_SCALE = 1.0e4  # the +-1e-4 initial table becomes uniform [-1, 1]
 OUT_ACTS = ["Sigmoid", "Exponential", "Tanh", "Softplus", "LeakyReLU", "Squareplus", "ReLU"]
 BRANCHY = ("relu", "leakyrelu")
 FUSED_SHAPES = [(64, 2), (64, 1), (32, 2), (32, 1)]  # TCNN_FUSED_SHAPES, IN = 32
+GRID_ENCS = {"grid": 2, "grid3": 3}  # the GRID encoding on two / three input dimensions
 
 
 class Case:
@@ -45,8 +46,8 @@ class Case:
             self.n_in, self.IN, self.enc_cfg = 16, 16, None
         elif enc == "identity5":  # 5 inputs, 11 padding columns of ones
             self.n_in, self.IN, self.enc_cfg = 5, 16, None
-        elif enc == "grid":
-            self.n_in, self.IN, self.enc_cfg = 2, 32, GRID
+        elif enc in GRID_ENCS:
+            self.n_in, self.IN, self.enc_cfg = GRID_ENCS[enc], 32, GRID
         else:  # "oneblob16" / "oneblob64" on two dimensions
             nb = int(enc[len("oneblob"):])
             self.n_in, self.IN, self.enc_cfg = 2, 2 * nb, {"otype": "OneBlob", "n_bins": nb}
@@ -70,6 +71,9 @@ def _cases():
     for W, NH in FUSED_SHAPES:  # register kernel without dL/dinput, tile kernel with it
         for act in ("None", "ReLU"):
             c.append(Case("register", "grid", W, NH, act, nodx="register", dx="tile"))
+    for W, NH in ((64, 2), (32, 1)):  # the D = 3 instantiations of the register kernel
+        for act in ("None", "ReLU"):
+            c.append(Case("register", "grid3", W, NH, act, nodx="register", dx="tile"))
     for W, NHs in ((16, (1, 3)), (32, (2, 5)), (64, (3,)), (128, (1, 4))):
         for NH in NHs:
             for enc in ("identity", "oneblob16" if W <= 32 else "oneblob64"):
@@ -155,6 +159,10 @@ SCALES = {
     "grid-w32h2-ReLU-o16": 1.5,
     "grid-w32h1-None-o16": 1.4,
     "grid-w32h1-ReLU-o16": 1.6,
+    "grid3-w64h2-None-o16": 1.4,
+    "grid3-w64h2-ReLU-o16": 1.6,
+    "grid3-w32h1-None-o16": 1.6,
+    "grid3-w32h1-ReLU-o16": 1.8,
     "identity-w16h1-None-o16": 1.2,
     "identity-w16h1-ReLU-o16": 1.6,
     "oneblob16-w16h1-None-o16": 2.1,
@@ -227,11 +235,12 @@ AGG_SEEDS = {"tile-identity-F-w128h4-ReLU-None-o3": 1}
 def host_params32(case, seed=SEED):
     """tcnn_module_initialize_params(seed) restated with the oracle's generators: pcg32{seed}, Xavier
     uniform per matrix in layout order, then the grid table uniform +-1e-4 (float32 [network | grid])"""
-    return init_params32(case.W, case.IN, case.NH, case.OUTP, GRID if case.enc == "grid" else None, seed)
+    return init_params32(case.W, case.IN, case.NH, case.OUTP, GRID if case.enc in GRID_ENCS else None, seed,
+                         n_dims=GRID_ENCS.get(case.enc, 2))
 
 
-def init_params32(W, IN, NH, OUTP, grid=None, seed=SEED):
-    """host_params32 for any network; grid: the grid encoding's config (two input dimensions) or None"""
+def init_params32(W, IN, NH, OUTP, grid=None, seed=SEED, n_dims=2):
+    """host_params32 for any network; grid: the grid encoding's config (on n_dims input dimensions) or None"""
     rng = O.pcg32(seed)
     shapes = [(OUTP, IN)] if NH == 0 else [(W, IN)] + [(W, W)] * (NH - 1) + [(OUTP, W)]
     parts = []
@@ -240,7 +249,7 @@ def init_params32(W, IN, NH, OUTP, grid=None, seed=SEED):
         O.lib().orc_xavier_uniform(ctypes.byref(rng), r, cc, m.ctypes.data_as(ctypes.c_void_p), 1.0)
         parts.append(m)
     if grid is not None:
-        parts.append(O.generate_uniform(rng, O.grid_cfg(grid, 2).n_params, -1e-4, 1e-4))
+        parts.append(O.generate_uniform(rng, O.grid_cfg(grid, n_dims).n_params, -1e-4, 1e-4))
     return np.concatenate(parts)
 
 
@@ -257,8 +266,8 @@ def encode(case, params16, x):
     """the encoded rows [B][IN] (fp16 bits) the network sees, with the oracle's encoders"""
     if case.enc.startswith("identity"):
         return O.identity_fwd(x, n_pad=case.IN - case.n_in)
-    if case.enc == "grid":
-        return np.ascontiguousarray(O.grid_fwd(O.grid_cfg(GRID, 2), x, params16[case.n_mlp:]).T)
+    if case.enc in GRID_ENCS:
+        return np.ascontiguousarray(O.grid_fwd(O.grid_cfg(GRID, case.n_in), x, params16[case.n_mlp:]).T)
     return O.oneblob_fwd(x, case.enc_cfg["n_bins"])
 
 
@@ -270,7 +279,7 @@ def draw(case, params16, filtered, seed=0):
     if case.enc.startswith("identity"):
         x = O.h2f(O.f2h(rng.uniform(-1.0, 1.0, (n, case.n_in)).astype(np.float32)))
     else:
-        x = rng.uniform(0.0, 1.0, (n, 2)).astype(np.float32)
+        x = rng.uniform(0.0, 1.0, (n, case.n_in)).astype(np.float32)
     dout = np.zeros((B, case.OUTP), np.uint16)
     dout[:, :case.n_out] = O.f2h(rng.uniform(-1.0, 1.0, (B, case.n_out)).astype(np.float32))
     enc = encode(case, params16, x)

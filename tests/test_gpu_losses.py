@@ -71,6 +71,13 @@ CASES = {
     "tile_exp": (_slow(_net(CONFIG_HASH, n_neurons=128, n_hidden_layers=4, output_activation="Exponential")), "fused"),  # tile, !OP
     "layered": (_net(CONFIG_HASH, otype="CutlassMLP"), "layered"),
 }
+# name -> (config, engine) of other test modules that use the helpers below (tests/test_gpu_fused_variants.py: a 3-D
+# grid); not part of this module's parametrisations
+OTHER_CASES = {}
+
+
+def _case(case):
+    return CASES[case] if case in CASES else OTHER_CASES[case]
 
 
 def _with_loss(cfg, otype):
@@ -93,16 +100,16 @@ def targets_for(pos, dims):
     return np.ascontiguousarray(np.tile(rgb, (1, (dims + 2) // 3))[:, :dims])
 
 
-def select_samples(cfg, w32, dims, n_want):
-    """n_want (positions, targets) for the network of cfg at fp32 parameters w32: positive oracle predictions
+def select_samples(cfg, w32, dims, n_want, n_dims=2):
+    """n_want (positions [n_want, n_dims], targets) for the network of cfg at fp32 parameters w32: positive oracle predictions
     (asserted), clear of the ReLU boundaries (grid encodings) and of |p - t| < 8 * 2^-10 (at most 10 % dropped, asserted)"""
     w16 = O.f2h(w32)
     if cfg["encoding"]["otype"].lower() == "hashgrid":
-        pos, _ = relu_safe_grid_batch(cfg, w16, 2 * n_want)
+        pos, _ = relu_safe_grid_batch(cfg, w16, 2 * n_want, n_dims=n_dims)
     else:
-        pos, _ = make_batch(2 * n_want)
+        pos, _ = make_batch(2 * n_want, n_dims=n_dims)
     tgt = targets_for(pos, dims)
-    om = O.OracleModel({k: v for k, v in cfg.items() if k != "loss"}, 2, dims)
+    om = O.OracleModel({k: v for k, v in cfg.items() if k != "loss"}, n_dims, dims)
     om.w32[:] = w32
     om.w16[:] = w16
     pred = O.h2f(om.inference(pos, n_threads=4))[:, :dims]
@@ -114,30 +121,34 @@ def select_samples(cfg, w32, dims, n_want):
     return np.ascontiguousarray(pos[idx]), np.ascontiguousarray(tgt[idx])
 
 
+def _setup(case, dims, n_dims=2):
+    """(test parameters fp32, positions [1024, n_dims], targets [1024, dims]) of a case, computed once"""
+    return _setup_once(case, dims, n_dims)
+
+
 @functools.lru_cache(maxsize=None)
-def _setup(case, dims):
-    """(test parameters fp32, positions [1024, 2], targets [1024, dims]) of a case, computed once"""
+def _setup_once(case, dims, n_dims):
     from tinycudann import Trainer
-    cfg, _ = CASES[case]
-    t = Trainer(2, dims, cfg, seed=1337)
+    cfg, _ = _case(case)
+    t = Trainer(n_dims, dims, cfg, seed=1337)
     w = scaled_params(cfg, trainer_arrays(t)["w32"], t.n_network_params)
-    pos, tgt = select_samples(cfg, w, dims, 1024)
+    pos, tgt = select_samples(cfg, w, dims, 1024, n_dims)
     for a in (w, pos, tgt):
         a.setflags(write=False)
     return w, pos, tgt
 
 
-def _trainer(case, dims, otype):
+def _trainer(case, dims, otype, n_dims=2):
     from tinycudann import Trainer
-    cfg, engine = CASES[case]
-    t = Trainer(2, dims, _with_loss(cfg, otype), seed=1337)
+    cfg, engine = _case(case)
+    t = Trainer(n_dims, dims, _with_loss(cfg, otype), seed=1337)
     assert t.engine == engine, (case, t.engine)
-    t.set_params_full_precision(_setup(case, dims)[0])
+    t.set_params_full_precision(_setup(case, dims, n_dims)[0])
     return t
 
 
-def _batch(torch, case, dims, B, step=0):
-    _, pos, tgt = _setup(case, dims)
+def _batch(torch, case, dims, B, step=0, n_dims=2):
+    _, pos, tgt = _setup(case, dims, n_dims)
     s = slice(step * B % 1024, step * B % 1024 + B)
     return torch.from_numpy(pos[s].copy()).cuda(), torch.from_numpy(tgt[s].copy()).cuda()
 

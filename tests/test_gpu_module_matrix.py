@@ -156,8 +156,8 @@ def _verify(case, p16, x, enc, dout, got, per_element, kind):
         if not (per_element and case.branchy):
             ratios["agg_in"] = _oneblob_dx_check(case, x, ref, dx, False)
             assert ratios["agg_in"] <= bar, ("dinput rel L2", ratios["agg_in"], bar)
-    if case.enc == "grid":  # the grid's own backward, unchanged by the case: the existing relative-L2 bars
-        g = O.grid_cfg(C.GRID, 2)
+    if case.enc in C.GRID_ENCS:  # the grid's own backward, unchanged by the case: the existing relative-L2 bars
+        g = O.grid_cfg(C.GRID, case.n_in)
         denc_soa = np.ascontiguousarray(O.f2h(ref["dinput"].astype(np.float32)).T)
         e = rel_err(grad[case.n_mlp:], O.grid_bwd(g, x, denc_soa))
         assert e <= 1e-3, ("grid gradient rel L2", e)
