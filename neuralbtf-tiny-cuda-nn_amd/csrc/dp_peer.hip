@@ -34,6 +34,8 @@
 // memory that the next step (or gather) turns into an exception -- a dead peer cannot hang the GPU.
 #include <cstdlib>
 #include <cstring>
+#include <map>
+#include <mutex>
 #include <vector>
 
 #include "adam_device.h"
@@ -280,6 +282,46 @@ __global__ __launch_bounds__(256) void k_peer_stage(const float* __restrict__ w3
 	stage[3 * stride + i] = steps[i];
 }
 
+// The exchange buffers' allocator. Uncached device memory that kernels have read is never handed
+// back to the driver: on a virtualised MI355X, hipFree of these blocks at detach left the process's
+// later ordinary allocations unreliable -- a trainer created after the detach computed a 2^18-point
+// grid gradient with ~700 entries of one hashed level (another level each run) a few per cent off,
+// while the same step before the attach, and after a detach that keeps the blocks, is exact. (Seen,
+// not explained: presumably the recycled range keeps its uncached mapping for some of its pages.)
+// A detached exchange parks its blocks here instead and the next export on the same device takes
+// the smallest one that fits, so a process that attaches and detaches repeatedly holds about the
+// blocks of its largest attachment. The process's exit releases them.
+struct UncachedPool {
+	std::mutex mu;
+	std::multimap<std::pair<int, size_t>, void*> parked;  // (device, bytes) -> block
+};
+UncachedPool& uncached_pool() {
+	static UncachedPool* p = new UncachedPool;  // never destroyed: trainers may outlive static destruction order
+	return *p;
+}
+void* uncached_take(int device, size_t bytes, size_t* block_bytes) {
+	{
+		UncachedPool& P = uncached_pool();
+		std::lock_guard<std::mutex> lk(P.mu);
+		auto it = P.parked.lower_bound({device, bytes});
+		if (it != P.parked.end() && it->first.first == device) {
+			void* p = it->second;
+			*block_bytes = it->first.second;
+			P.parked.erase(it);
+			return p;
+		}
+	}
+	void* p = nullptr;
+	TCNN_HIP_CHECK(hipExtMallocWithFlags(&p, bytes, hipDeviceMallocUncached));
+	*block_bytes = bytes;
+	return p;
+}
+void uncached_park(int device, size_t block_bytes, void* p) {
+	UncachedPool& P = uncached_pool();
+	std::lock_guard<std::mutex> lk(P.mu);
+	P.parked.emplace(std::make_pair(device, block_bytes), p);
+}
+
 }  // namespace
 
 struct TrainerHost::PeerDp {
@@ -291,6 +333,8 @@ struct TrainerHost::PeerDp {
 	// uncached, exported: gradient sums [N*per] fp32, fp16 shard mirror [N*per], state staging
 	// [4][N*per] (w32, m1, m2, steps), counters [64] uint32
 	void* x[PEER_NBUF] = {nullptr, nullptr, nullptr, nullptr};
+	size_t x_block[PEER_NBUF] = {0, 0, 0, 0};  // bytes of the pool block behind x[k] (>= what the exchange uses)
+	int device = 0;
 	std::vector<void*> opened;  // IPC mappings of the peers' buffers
 	std::vector<void*> host_ptr;  // [PEER_NBUF][nranks] the same pointers as `ptrs`, host copy (kernel arguments)
 	int* err_host = nullptr;
@@ -309,8 +353,8 @@ struct TrainerHost::PeerDp {
 		// dp_peer_detach's SLOT_DETACH wait)
 		(void)hipDeviceSynchronize();
 		for (void* p : opened) (void)hipIpcCloseMemHandle(p);
-		for (void* p : x)
-			if (p) (void)hipFree(p);
+		for (int k = 0; k < PEER_NBUF; ++k)  // parked, not freed (UncachedPool)
+			if (x[k]) uncached_park(device, x_block[k], x[k]);
 		if (err_host) (void)hipHostFree(err_host);
 	}
 	template <typename T>
@@ -380,9 +424,12 @@ void TrainerHost::dp_peer_export(int nranks, int rank, void* blob_out) {
 	grow_keep(m1, pad * 4, n_params * 4);
 	grow_keep(m2, pad * 4, n_params * 4);
 	grow_keep(steps, pad * 4, n_params * 4);
+	int dev = 0;
+	TCNN_HIP_CHECK(hipGetDevice(&dev));
+	pd->device = dev;
 	const size_t xbytes[PEER_NBUF] = {pad * 4, pad * 2, 4 * pad * 4, 256};
 	for (int k = 0; k < PEER_NBUF; ++k) {
-		TCNN_HIP_CHECK(hipExtMallocWithFlags(&pd->x[k], xbytes[k], hipDeviceMallocUncached));
+		pd->x[k] = uncached_take(dev, xbytes[k], &pd->x_block[k]);
 		TCNN_HIP_CHECK(hipMemset(pd->x[k], 0, xbytes[k]));
 	}
 	pd->ctr.reserve(64);
@@ -390,8 +437,7 @@ void TrainerHost::dp_peer_export(int nranks, int rank, void* blob_out) {
 	TCNN_HIP_CHECK(hipHostMalloc((void**)&pd->err_host, 64, hipHostMallocMapped));
 	*pd->err_host = 0;
 	TCNN_HIP_CHECK(hipHostGetDevicePointer((void**)&pd->err_dev, pd->err_host, 0));
-	int dev = 0, khz = 0;
-	TCNN_HIP_CHECK(hipGetDevice(&dev));
+	int khz = 0;
 	TCNN_HIP_CHECK(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev));
 	pd->clock_khz = std::max(khz, 1);
 	pd->timeout_ticks = (long long)((double)pd->clock_khz * 1000.0 * peer_timeout_s);
