@@ -399,12 +399,17 @@ int tcnn_trainer_initialize_params_rng(tcnn_trainer* t, uint64_t* state, uint64_
  * training and for network->inference ("fused": the whole MLP in one launch). */
 const char* tcnn_trainer_engine(const tcnn_trainer* t);
 const char* tcnn_trainer_inference_engine(const tcnn_trainer* t);
-/* The same for a network module (NetworkWithInputEncoding / create_network); "encoding" for encodings. */
+/* The same for a network module (NetworkWithInputEncoding / create_network); "encoding" for encodings. An Fp32
+ * network module is "fused" for both (the whole MLP in one register-resident launch) when its network is
+ * FullyFusedMLP with at least one hidden layer and 16, 32, 64 or 128 neurons, else "layered" (one launch per
+ * layer); the two give the same bits. */
 const char* tcnn_module_engine(const tcnn_module* m);
 const char* tcnn_module_inference_engine(const tcnn_module* m);
 /* The kernel family tcnn_module_backward runs for this module, with or without dL/dinput requested:
  * "register" (grid + W <= 64 in one register-resident kernel; never with dL/dinput), "tile", "layered";
- * "encoding" for encodings. */
+ * "encoding" for encodings. An Fp32 network module whose engine is "fused" names "chain" for either flag: one
+ * launch carries dL/dy down to dL/d(encoding) in registers (and stores nothing else when dL/dparams is not
+ * asked for), then one weight-gradient launch per layer; every other Fp32 network module names "layered". */
 const char* tcnn_module_backward_kernel(const tcnn_module* m, int with_dinput);
 /* set_max_level on the trainer model's grid encoding (see tcnn_module_set_max_level) */
 int tcnn_trainer_set_max_level(tcnn_trainer* t, float max_level);

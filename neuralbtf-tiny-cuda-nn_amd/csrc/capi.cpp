@@ -287,9 +287,10 @@ struct ModuleNWIEF32 : ModuleBase {
 		                              (float*)dL_dparams, (float*)dL_ddLdout, dL_din);
 	}
 	GridEncodingHost* grid_encoding() override { return model.enc->lone_grid(); }
-	const char* engine() const override { return "layered"; }
-	const char* inference_engine() const override { return "layered"; }
-	const char* backward_kernel(bool) const override { return "layered"; }
+	// "fused" / "chain": the whole network in one launch (mlp_f32_fused.hip); the weight gradients stay per layer
+	const char* engine() const override { return model.fused_ok() ? "fused" : "layered"; }
+	const char* inference_engine() const override { return engine(); }
+	const char* backward_kernel(bool) const override { return model.fused_ok() ? "chain" : "layered"; }
 	uint32_t n_input_dims() const override { return model.n_input_dims; }
 	uint32_t n_output_dims() const override { return model.mlp.padded_output; }
 	uint64_t n_params() const override { return model.n_params(); }

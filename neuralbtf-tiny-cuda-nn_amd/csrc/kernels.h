@@ -468,6 +468,18 @@ void launch_f32_layer_curvature(hipStream_t st, uint32_t B, uint32_t N, uint32_t
 void launch_f32_identity_tangent(hipStream_t st, uint32_t B, uint32_t D, uint32_t width, float scale, const float* u_x, float* u0);
 // dst[i] += src[i], i < n
 void launch_f32_add(hipStream_t st, size_t n, float* dst, const float* src);
+// The whole network in one launch (mlp_f32_fused.hip): NH >= 1 hidden layers of a width below, IN and OUTP multiples
+// of 16, B of 128. params = [W0 [W][IN] | W1 .. W_{NH-1} [W][W] | Wout [OUTP][W]]. Every value is the layer kernels' to the bit.
+inline bool f32_mlp_fused_width_ok(uint32_t W) { return W == 16 || W == 32 || W == 64 || W == 128; }
+// y[B][OUTP] = out_act(Wout act(.. act(W0 e))), e [B][IN]; hidden_keep (nullable): the NH hidden activations [NH][B][W];
+// y2 (nullable): a second copy of y
+void launch_f32_mlp_fwd(hipStream_t st, uint32_t B, uint32_t IN, uint32_t W, uint32_t NH, uint32_t OUTP, const float* params, const float* e,
+                        float* hidden_keep, float* y, float* y2, int act, int out_act);
+// the backward's delta chain from dy = dL/dy [B][OUTP] and keep = [e | NH hidden activations | y] of the forward:
+// d_hidden (nullable) [NH][B][W] = dL/d(hidden activation) of every layer, as launch_f32_wgrad reads them; d0 (nullable)
+// [B][IN] = dL/de
+void launch_f32_mlp_bwd_chain(hipStream_t st, uint32_t B, uint32_t IN, uint32_t W, uint32_t NH, uint32_t OUTP, const float* params,
+                              const float* dy, const float* keep, float* d_hidden, float* d0, int act, int out_act);
 
 void launch_probe_hfma(hipStream_t st, const void* a, const void* b, const void* c, void* out, uint32_t n_pairs);
 // Diagnostic: the config_hash fused (pipelined) kernel with s_memtime phase stamps (prof: [blocks*8][8] u64).

@@ -1295,8 +1295,23 @@ json NetworkF32Host::hyperparams() const {
 	return {{"otype", "NetworkWithInputEncoding"}, {"encoding", enc->hyperparams()}, {"network", mlp.hyperparams()}};
 }
 
+bool NetworkF32Host::fused_ok() const {
+	const bool ff = ieq(mlp.otype, "FullyFusedMLP") || ieq(mlp.otype, "MegakernelMLP");
+	return ff && mlp.n_hidden_layers >= 1 && f32_mlp_fused_width_ok(mlp.width);
+}
+
 void NetworkF32Host::forward(hipStream_t st, uint32_t B, const float* pos, const float* params, float* out32, float* keep) {
 	const uint32_t W = mlp.width, IN = mlp.n_input, NH = mlp.n_hidden_layers, OUTP = mlp.padded_output;
+	if (fused_ok()) {  // one launch; without a keep nothing but the encoded rows and the output touches memory
+		if (!keep) acts.reserve((size_t)B * IN * 4);
+		float* e = keep ? keep : acts.as<float>();
+		float* h = keep ? e + (size_t)B * IN : nullptr;
+		enc->forward_aos(st, B, pos, params + mlp.n_params(), e);
+		// with a keep the output lands there (the backward's output-activation transfer reads it) and at the caller's
+		launch_f32_mlp_fwd(st, B, IN, W, NH, OUTP, params, e, h, keep ? h + (size_t)NH * B * W : out32, keep ? out32 : nullptr, mlp.activation,
+		                   mlp.output_activation);
+		return;
+	}
 	if (!keep) acts.reserve(((size_t)B * IN + 2 * (size_t)B * W) * 4);
 	float* e = keep ? keep : acts.as<float>();
 	float* h = e + (size_t)B * IN;
@@ -1329,7 +1344,10 @@ void NetworkF32Host::backward(hipStream_t st, uint32_t B, const float* pos, cons
 	const float* eparams = params + n_mlp;
 	const uint32_t nsl = f32_wgrad_n_slabs(B);
 	const uint32_t maxK = std::max(W, IN);
-	delta0.reserve((size_t)B * maxK * 4);
+	const bool fused = fused_ok();
+	// layer kernels: two ping-pong deltas. Fused chain: delta0 = the hidden layers' deltas [NH][B][W], which only the
+	// weight gradients read; delta1 = D_0 = dL/d(encoded row)
+	delta0.reserve(fused ? (dL_dparams ? (size_t)NH * B * W * 4 : 0) : (size_t)B * maxK * 4);
 	delta1.reserve((size_t)B * maxK * 4);
 	if (dL_dparams) wgrad_partial.reserve((size_t)nsl * std::max(W, OUTP) * maxK * 4);
 	// weight offsets [W0 | W1 .. W_{NH-1} | Wout] ([Wout] alone for 0 hidden layers)
@@ -1346,7 +1364,15 @@ void NetworkF32Host::backward(hipStream_t st, uint32_t B, const float* pos, cons
 	float* dnext = delta1.as<float>();
 	const bool enc_grad = (dL_dparams && enc->n_params() > 0) || dL_dinput;
 	// a delta here is dL/d(post-activation value): both of its readers apply the transfer as they load it
-	if (NH == 0) {
+	if (fused) {  // the whole chain in one launch, then the weight gradients from what it stored
+		float* dh = dL_dparams ? dcur : nullptr;
+		launch_f32_mlp_bwd_chain(st, B, IN, W, NH, OUTP, params, dout32, keep, dh, enc_grad ? dnext : nullptr, mlp.activation,
+		                         mlp.output_activation);
+		auto d = [&](uint32_t j) { return dh + (size_t)j * B * W; };
+		wgrad(OUTP, W, dout32, y, mlp.output_activation, act(NH - 1), w_off(NH));
+		for (uint32_t j = NH - 1; j >= 1; --j) wgrad(W, W, d(j), act(j), mlp.activation, act(j - 1), w_off(j));
+		wgrad(W, IN, d(0), act(0), mlp.activation, e, 0);
+	} else if (NH == 0) {
 		wgrad(OUTP, IN, dout32, y, mlp.output_activation, e, 0);
 		if (enc_grad) launch_f32_layer_bwd(st, B, OUTP, IN, params, dout32, y, mlp.output_activation, dnext);
 	} else {

@@ -502,8 +502,10 @@ private:
 // NetworkWithInputEncoding<float>: an fp32 network module (Network / NetworkWithInputEncoding dtype = float32).
 // The fp32 EncodingHost in front, its rows handed to the first layer as they are, then one f32-MFMA kernel per
 // layer (mlp_f32.hip). Parameters [mlp | encoding], rows, dL/dy, dL/dparams and dL/dinput are all fp32; layout,
-// parameter count, initial values, hyperparams() follow NetworkHost for the same config. FullyFusedMLP and
-// CutlassMLP run the same kernels. Sine (no backward from its forward value) is served by inference() only.
+// parameter count, initial values, hyperparams() follow NetworkHost for the same config. FullyFusedMLP with at
+// least one hidden layer (fused_ok) runs the forward and the backward's delta chain as one register-resident launch
+// each (mlp_f32_fused.hip); CutlassMLP, and FullyFusedMLP without a hidden layer, run the layer kernels. Both give the
+// same bits. Sine (no backward from its forward value) is served by inference() only.
 struct NetworkF32Host {
 	EngineSwitches sw = EngineSwitches::from_env();
 	std::unique_ptr<EncodingHost> enc;
@@ -513,6 +515,8 @@ struct NetworkF32Host {
 	NetworkF32Host(uint32_t n_in, uint32_t n_out, const json& enc, const json& net);
 	uint64_t n_params() const { return (uint64_t)mlp.n_params() + enc->n_params(); }
 	bool has_sine() const { return mlp.activation == ACT_SINE || mlp.output_activation == ACT_SINE; }
+	// forward() and backward() run the fused kernels: FullyFusedMLP, NH >= 1, W in {16, 32, 64, 128}
+	bool fused_ok() const;
 	void initialize_params(Pcg32& rng, float* host_out, float scale = 1.0f) const;
 	json hyperparams() const;
 	// what a forward keeps for its backward: [enc B x IN | NH hidden activations B x W | output B x OUTP] floats

@@ -153,8 +153,8 @@ class _NativeModule:
         return L.lib().tcnn_module_inference_engine(self.h).decode()
 
     def backward_kernel(self, with_dinput):
-        """the kernel family a backward runs, with or without dL/dinput: "register", "tile", "layered"
-        ("encoding" for encodings)"""
+        """the kernel family a backward runs, with or without dL/dinput: "register", "tile", "layered", "chain" (a
+        fused fp32 network module; "encoding" for encodings)"""
         return L.lib().tcnn_module_backward_kernel(self.h, int(bool(with_dinput))).decode()
 
     def initial_params(self, seed):

@@ -43,6 +43,11 @@ MFMA_WRITE_STATES = {
     "v_mfma_f32_16x16x32_bf16": 8,  # 4-pass
     "v_mfma_f32_32x32x16_f16": 16,  # 8-pass (12 on gfx950 per the guide; 16 is conservative)
     "v_mfma_f32_32x32x16_bf16": 16,
+    # the fp32 network kernels' MFMA: 8-pass, and an SGEMM rather than an XDL operation, for which LLVM's
+    # GCNHazardRecognizer asks passes + 2 (XDL: passes + 3, + 1 on gfx950). hipcc's own schedule agrees: the
+    # closest consumers in mlp_f32_fused.hip sit at exactly 10 states (34 sites), none below. Without this row
+    # every access within CAP states was reported, which the layer kernels (mlp_f32.hip) happened never to have.
+    "v_mfma_f32_16x16x4_f32": 10,
 }
 VALU_TO_MFMA_SRC_AB = 2
 # A taken branch is followed by an instruction-fetch bubble before the target issues; it counts one
