@@ -100,6 +100,29 @@ tcnn_context* tcnn_module_forward(tcnn_module* m, void* stream, uint32_t n, cons
 int tcnn_module_backward(tcnn_module* m, void* stream, const tcnn_context* ctx, uint32_t n, float* dL_dinput,
                          const void* dL_doutput, void* dL_dparams, const float* input, const void* output,
                          const void* params);
+/* The three calls above with a layout per matrix (the reference's GPUMatrixDynamic RM / CM). A bit set in
+ * `layouts` makes that matrix batch-contiguous ("SoA", the reference's RM): [width][n] at its unpadded width --
+ * input [n_input_dims][n], output and dL_doutput [the n_output_dims the module was created with][n] (no padding
+ * rows: n_output_dims * n elements are read or written, nothing more), dL_dinput [n_input_dims][n]. A bit clear
+ * keeps the rows of the calls above ("AoS", CM: [n][padded width]). layouts == 0 is the call above itself. Every
+ * result is the AoS call's to the bit, transposed. A context is layout-free: the backward of a forward may use
+ * any mask, but its `input` must keep the forward's layout (it is the same matrix).
+ * Served by Fp32 network modules whose network is FullyFusedMLP with at least one hidden layer (the fused kernels
+ * read and write either layout in place; behind an encoding other than a plain Identity the positions and
+ * dL_dinput pass through a transpose of n_input_dims floats per row). Any other module answers a non-zero mask with
+ * "<name>: batch-contiguous matrices are not implemented by the MI355X engine yet (fp32 FullyFusedMLP network
+ * modules only)". */
+#define TCNN_LAYOUT_SOA_INPUT 1u
+#define TCNN_LAYOUT_SOA_OUTPUT 2u
+#define TCNN_LAYOUT_SOA_DL_DOUTPUT 4u
+#define TCNN_LAYOUT_SOA_DL_DINPUT 8u
+int tcnn_module_inference_layout(tcnn_module* m, void* stream, uint32_t n, const float* input, void* output, const void* params,
+                                 uint32_t layouts);
+tcnn_context* tcnn_module_forward_layout(tcnn_module* m, void* stream, uint32_t n, const float* input, void* output,
+                                         const void* params, int prepare_input_gradients, uint32_t layouts);
+int tcnn_module_backward_layout(tcnn_module* m, void* stream, const tcnn_context* ctx, uint32_t n, float* dL_dinput,
+                                const void* dL_doutput, void* dL_dparams, const float* input, const void* output,
+                                const void* params, uint32_t layouts);
 /* The torch binding's backward with its loss-scale arithmetic folded in (reference
  * bindings/torch/tinycudann/modules.py:128-138): dL_doutput (fp16) is multiplied by loss_scale and
  * rounded to fp16, the module's backward runs on it, dL_dinput (fp32) is divided by loss_scale and

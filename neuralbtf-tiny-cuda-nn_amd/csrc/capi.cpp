@@ -110,6 +110,19 @@ struct ModuleBase {
 	                                     float*, const void*) {
 		throw std::runtime_error("DifferentiableObject::backward_backward_input_impl: not implemented error");
 	}
+	// The three calls with a non-zero layout mask (TCNN_LAYOUT_*): only an fp32 FullyFusedMLP network module serves them
+	void refuse_layouts() const {
+		throw std::runtime_error(name() + ": batch-contiguous matrices are not implemented by the MI355X engine yet (fp32 FullyFusedMLP network modules only)");
+	}
+	virtual void inference_layout(hipStream_t, uint32_t, const float*, void*, const void*, uint32_t) { refuse_layouts(); }
+	virtual std::unique_ptr<ModuleCtx> forward_layout(hipStream_t, uint32_t, const float*, void*, const void*, bool, uint32_t) {
+		refuse_layouts();
+		return nullptr;
+	}
+	virtual void backward_layout(hipStream_t, const ModuleCtx*, uint32_t, float*, const void*, void*, const float*, const void*, const void*,
+	                             uint32_t) {
+		refuse_layouts();
+	}
 	virtual GridEncodingHost* grid_encoding() { return nullptr; }
 	// precision of the parameters, the output, dL/doutput and dL/dparams (TCNN_PRECISION_*): fp16 for
 	// every module but an encoding or a network created with Fp32
@@ -239,38 +252,62 @@ struct ModuleNWIEF32 : ModuleBase {
 	ModuleNWIEF32(uint32_t n_in, uint32_t n_out, const json& enc, const json& net) : model(n_in, n_out, enc, net) {}
 	int precision() const override { return TCNN_PRECISION_FP32; }
 	void inference(hipStream_t st, uint32_t n, const float* in, void* out, const void* params) override {
-		check_batch(n);
-		model.forward(st, n, in, (const float*)params, (float*)out, nullptr);
+		inference_layout(st, n, in, out, params, 0);
 	}
-	std::unique_ptr<ModuleCtx> forward(hipStream_t st, uint32_t n, const float* in, void* out, const void* params, bool) override {
+	std::unique_ptr<ModuleCtx> forward(hipStream_t st, uint32_t n, const float* in, void* out, const void* params, bool prep) override {
+		return forward_layout(st, n, in, out, params, prep, 0);
+	}
+	void backward(hipStream_t st, const ModuleCtx* ctx, uint32_t n, float* dL_din, const void* dL_dout, void* dL_dparams, const float* in,
+	              const void* out, const void* params) override {
+		backward_layout(st, ctx, n, dL_din, dL_dout, dL_dparams, in, out, params, 0);
+	}
+	// mask 0 is the AoS call: the same launches with the same arguments
+	F32Layouts layouts(uint32_t mask) const {
+		TCNN_CHECK(mask < 16, "layouts: unknown bits in the mask");
+		if (mask && !model.fused_ok()) refuse_layouts();
+		return F32Layouts(mask);
+	}
+	void inference_layout(hipStream_t st, uint32_t n, const float* in, void* out, const void* params, uint32_t mask) override {
+		const F32Layouts lay = layouts(mask);
+		check_batch(n);
+		if (n) model.forward(st, n, in, (const float*)params, (float*)out, nullptr, lay);
+	}
+	std::unique_ptr<ModuleCtx> forward_layout(hipStream_t st, uint32_t n, const float* in, void* out, const void* params, bool,
+	                                          uint32_t mask) override {
+		const F32Layouts lay = layouts(mask);
 		check_batch(n);
 		TCNN_CHECK(!model.has_sine(), "Sine has no backward from its forward value: a forward that keeps a context is refused (use inference)");
 		auto c = std::make_unique<NwieF32Ctx>();
+		if (!n) return c;
 		if (model.sw.no_forward_keep) {  // A/B switch (read when the module is built): the backward recomputes the forward
-			model.forward(st, n, in, (const float*)params, (float*)out, nullptr);
+			model.forward(st, n, in, (const float*)params, (float*)out, nullptr, lay);
 			return c;
 		}
 		c->pool = pool;
 		c->keep = pool->get();
 		c->keep->reserve(model.keep_floats(n) * 4);
-		model.forward(st, n, in, (const float*)params, (float*)out, c->keep->as<float>());
+		model.forward(st, n, in, (const float*)params, (float*)out, c->keep->as<float>(), lay);
 		c->in = in;
 		c->params = params;
 		return c;
 	}
-	void backward(hipStream_t st, const ModuleCtx* ctx, uint32_t n, float* dL_din, const void* dL_dout, void* dL_dparams, const float* in,
-	              const void*, const void* params) override {
+	void backward_layout(hipStream_t st, const ModuleCtx* ctx, uint32_t n, float* dL_din, const void* dL_dout, void* dL_dparams,
+	                     const float* in, const void*, const void* params, uint32_t mask) override {
+		const F32Layouts lay = layouts(mask);
 		check_batch(n);
-		if (!dL_dparams && !dL_din) return;
-		model.backward(st, n, in, (const float*)params, (const float*)dL_dout, kept(st, ctx, n, in, params), (float*)dL_dparams, dL_din);
+		if (!n || (!dL_dparams && !dL_din)) return;
+		model.backward(st, n, in, (const float*)params, (const float*)dL_dout, kept(st, ctx, n, in, params, lay.input), (float*)dL_dparams,
+		               dL_din, lay);
 	}
 	// the context's activations if they describe this batch (the backward sees the forward's input and parameters),
-	// else the forward again into the module's own buffer
-	const float* kept(hipStream_t st, const ModuleCtx* ctx, uint32_t n, const float* in, const void* params) {
+	// else the forward again into the module's own buffer (the context is AoS whatever the input's layout)
+	const float* kept(hipStream_t st, const ModuleCtx* ctx, uint32_t n, const float* in, const void* params, bool in_soa = false) {
 		const NwieF32Ctx* c = dynamic_cast<const NwieF32Ctx*>(ctx);
 		if (c && c->keep && c->in == in && c->params == params) return c->keep->as<float>();
 		rekeep.reserve(model.keep_floats(n) * 4);
-		model.forward(st, n, in, (const float*)params, nullptr, rekeep.as<float>());
+		F32Layouts lay;
+		lay.input = in_soa;
+		model.forward(st, n, in, (const float*)params, nullptr, rekeep.as<float>(), lay);
 		return rekeep.as<float>();
 	}
 	// Second order with respect to the input (beyond the reference, whose networks have none): every non-null
@@ -526,6 +563,34 @@ int tcnn_module_backward(tcnn_module* m, void* stream, const tcnn_context* ctx, 
 		}
 		TCNN_CHECK(ctx->n == n, "backward: batch size differs from the forward's");
 		m->m->backward((hipStream_t)stream, ctx->impl.get(), n, dL_din, dL_dout, dL_dparams, in, out, params);
+	});
+}
+
+// The three entries above with a layout mask; 0 is the entry above itself.
+int tcnn_module_inference_layout(tcnn_module* m, void* stream, uint32_t n, const float* in, void* out, const void* params, uint32_t layouts) {
+	if (!layouts) return tcnn_module_inference(m, stream, n, in, out, params);
+	return guard([&] { m->m->inference_layout((hipStream_t)stream, n, in, out, params, layouts); });
+}
+
+tcnn_context* tcnn_module_forward_layout(tcnn_module* m, void* stream, uint32_t n, const float* in, void* out, const void* params, int prep,
+                                         uint32_t layouts) {
+	if (!layouts) return tcnn_module_forward(m, stream, n, in, out, params, prep);
+	return guard_ptr<tcnn_context>([&] {
+		auto c = std::make_unique<tcnn_context>();
+		c->n = n;
+		c->impl = m->m->forward_layout((hipStream_t)stream, n, in, out, params, prep != 0, layouts);
+		return c.release();
+	});
+}
+
+int tcnn_module_backward_layout(tcnn_module* m, void* stream, const tcnn_context* ctx, uint32_t n, float* dL_din, const void* dL_dout,
+                                void* dL_dparams, const float* in, const void* out, const void* params, uint32_t layouts) {
+	if (!layouts) return tcnn_module_backward(m, stream, ctx, n, dL_din, dL_dout, dL_dparams, in, out, params);
+	return guard([&] {
+		TCNN_CHECK(ctx != nullptr, "backward: null context");
+		TCNN_CHECK(ctx->n == n, "backward: batch size differs from the forward's");
+		m->m->backward_layout((hipStream_t)stream, ctx->impl.get(), n, dL_din, dL_dout, dL_dparams, in, out, params, layouts);
+		if (n == 0 && dL_dparams) TCNN_HIP_CHECK(hipMemsetAsync(dL_dparams, 0, m->m->n_params() * m->m->elem_bytes(), (hipStream_t)stream));
 	});
 }
 

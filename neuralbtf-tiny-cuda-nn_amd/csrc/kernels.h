@@ -480,6 +480,21 @@ void launch_f32_mlp_fwd(hipStream_t st, uint32_t B, uint32_t IN, uint32_t W, uin
 // [B][IN] = dL/de
 void launch_f32_mlp_bwd_chain(hipStream_t st, uint32_t B, uint32_t IN, uint32_t W, uint32_t NH, uint32_t OUTP, const float* params,
                               const float* dy, const float* keep, float* d_hidden, float* d0, int act, int out_act);
+// The two launches above with a layout per batch-side operand: AoS [B][width] as above, or batch-contiguous (SoA)
+// [width][B] without padding, n_out <= OUTP being the output's unpadded width. Every value is the AoS launch's to the
+// bit, transposed; all flags false is the AoS launch itself.
+// e_soa: e is [IN][B] and e_keep (nullable) receives it as [B][IN] for the context. y2_soa: y2 is the caller's
+// [n_out][B] and y (nullable) the context's [B][OUTP]; nothing past neuron n_out of y2 is written.
+void launch_f32_mlp_fwd_layout(hipStream_t st, uint32_t B, uint32_t IN, uint32_t W, uint32_t NH, uint32_t OUTP, uint32_t n_out,
+                               const float* params, const float* e, bool e_soa, float* e_keep, float* hidden_keep, float* y, float* y2,
+                               bool y2_soa, int act, int out_act);
+// dy_soa: dy is [n_out][B] (padded neurons count as exact zeros) and dy_aos (nullable) receives it as zero-padded
+// [B][OUTP] rows, which launch_f32_wgrad reads. d0_soa: d0 is [IN][B].
+void launch_f32_mlp_bwd_chain_layout(hipStream_t st, uint32_t B, uint32_t IN, uint32_t W, uint32_t NH, uint32_t OUTP, uint32_t n_out,
+                                     const float* params, const float* dy, bool dy_soa, float* dy_aos, const float* keep, float* d_hidden,
+                                     float* d0, bool d0_soa, int act, int out_act);
+// dst[C][R] = src[R][C]^T
+void launch_f32_transpose(hipStream_t st, uint32_t R, uint32_t C, const float* src, float* dst);
 
 void launch_probe_hfma(hipStream_t st, const void* a, const void* b, const void* c, void* out, uint32_t n_pairs);
 // Diagnostic: the config_hash fused (pipelined) kernel with s_memtime phase stamps (prof: [blocks*8][8] u64).

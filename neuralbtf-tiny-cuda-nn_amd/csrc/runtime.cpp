@@ -1300,16 +1300,32 @@ bool NetworkF32Host::fused_ok() const {
 	return ff && mlp.n_hidden_layers >= 1 && f32_mlp_fused_width_ok(mlp.width);
 }
 
-void NetworkF32Host::forward(hipStream_t st, uint32_t B, const float* pos, const float* params, float* out32, float* keep) {
+bool NetworkF32Host::soa_first_layer() const {
+	const EncodingHost::Part* p = enc->lone_part();
+	return p && p->kind == COMP_IDENTITY && p->f0 == 1.0f && p->f1 == 0.0f && p->width == p->n_values;
+}
+
+const float* NetworkF32Host::aos_positions(hipStream_t st, uint32_t B, const float* pos_soa) {
+	pos_aos.reserve((size_t)B * n_input_dims * 4);
+	launch_f32_transpose(st, n_input_dims, B, pos_soa, pos_aos.as<float>());
+	return pos_aos.as<float>();
+}
+
+void NetworkF32Host::forward(hipStream_t st, uint32_t B, const float* pos, const float* params, float* out32, float* keep, F32Layouts lay) {
 	const uint32_t W = mlp.width, IN = mlp.n_input, NH = mlp.n_hidden_layers, OUTP = mlp.padded_output;
+	TCNN_CHECK(!lay.any() || fused_ok(), "fp32 network: batch-contiguous matrices need the fused kernels (FullyFusedMLP)");
 	if (fused_ok()) {  // one launch; without a keep nothing but the encoded rows and the output touches memory
-		if (!keep) acts.reserve((size_t)B * IN * 4);
+		const bool direct = lay.input && soa_first_layer();  // the first layer reads the caller's [IN][B] itself
+		const bool y_soa = lay.output && out32;
+		if (lay.input && !direct) pos = aos_positions(st, B, pos);
+		if (!keep && !direct) acts.reserve((size_t)B * IN * 4);
 		float* e = keep ? keep : acts.as<float>();
 		float* h = keep ? e + (size_t)B * IN : nullptr;
-		enc->forward_aos(st, B, pos, params + mlp.n_params(), e);
+		float* yk = keep ? h + (size_t)NH * B * W : nullptr;
+		if (!direct) enc->forward_aos(st, B, pos, params + mlp.n_params(), e);
 		// with a keep the output lands there (the backward's output-activation transfer reads it) and at the caller's
-		launch_f32_mlp_fwd(st, B, IN, W, NH, OUTP, params, e, h, keep ? h + (size_t)NH * B * W : out32, keep ? out32 : nullptr, mlp.activation,
-		                   mlp.output_activation);
+		launch_f32_mlp_fwd_layout(st, B, IN, W, NH, OUTP, n_output_dims, params, direct ? pos : e, direct, direct ? keep : nullptr, h,
+		                          y_soa || keep ? yk : out32, y_soa || keep ? out32 : nullptr, y_soa, mlp.activation, mlp.output_activation);
 		return;
 	}
 	if (!keep) acts.reserve(((size_t)B * IN + 2 * (size_t)B * W) * 4);
@@ -1333,8 +1349,10 @@ void NetworkF32Host::forward(hipStream_t st, uint32_t B, const float* pos, const
 }
 
 void NetworkF32Host::backward(hipStream_t st, uint32_t B, const float* pos, const float* params, const float* dout32, const float* keep,
-                              float* dL_dparams, float* dL_dinput) {
+                              float* dL_dparams, float* dL_dinput, F32Layouts lay) {
 	TCNN_CHECK(!has_sine(), "Sine has no backward from its forward value: the MI355X engine serves it through inference only");
+	TCNN_CHECK(!lay.any() || fused_ok(), "fp32 network: batch-contiguous matrices need the fused kernels (FullyFusedMLP)");
+	if (lay.input && !soa_first_layer()) pos = aos_positions(st, B, pos);  // the encoding's backward reads AoS positions
 	const uint32_t W = mlp.width, IN = mlp.n_input, NH = mlp.n_hidden_layers, OUTP = mlp.padded_output;
 	const uint32_t n_mlp = mlp.n_params();
 	const float* e = keep;
@@ -1366,10 +1384,19 @@ void NetworkF32Host::backward(hipStream_t st, uint32_t B, const float* pos, cons
 	// a delta here is dL/d(post-activation value): both of its readers apply the transfer as they load it
 	if (fused) {  // the whole chain in one launch, then the weight gradients from what it stored
 		float* dh = dL_dparams ? dcur : nullptr;
-		launch_f32_mlp_bwd_chain(st, B, IN, W, NH, OUTP, params, dout32, keep, dh, enc_grad ? dnext : nullptr, mlp.activation,
-		                         mlp.output_activation);
+		// a SoA dL/dy reaches the output layer's weight gradient as the zero-padded rows the chain writes beside its read
+		float* dya = nullptr;
+		if (lay.dL_doutput && dL_dparams) {
+			dy_aos.reserve((size_t)B * OUTP * 4);
+			dya = dy_aos.as<float>();
+		}
+		const bool d0_direct = lay.dL_dinput && dL_dinput && soa_first_layer();  // dL/dinput is D_0: the chain writes it
+		launch_f32_mlp_bwd_chain_layout(st, B, IN, W, NH, OUTP, n_output_dims, params, dout32, lay.dL_doutput, dya, keep, dh,
+		                                d0_direct ? dL_dinput : enc_grad ? dnext : nullptr, d0_direct, mlp.activation,
+		                                mlp.output_activation);
+		if (d0_direct) dL_dinput = nullptr;
 		auto d = [&](uint32_t j) { return dh + (size_t)j * B * W; };
-		wgrad(OUTP, W, dout32, y, mlp.output_activation, act(NH - 1), w_off(NH));
+		wgrad(OUTP, W, lay.dL_doutput ? dya : dout32, y, mlp.output_activation, act(NH - 1), w_off(NH));
 		for (uint32_t j = NH - 1; j >= 1; --j) wgrad(W, W, d(j), act(j), mlp.activation, act(j - 1), w_off(j));
 		wgrad(W, IN, d(0), act(0), mlp.activation, e, 0);
 	} else if (NH == 0) {
@@ -1386,7 +1413,13 @@ void NetworkF32Host::backward(hipStream_t st, uint32_t B, const float* pos, cons
 		wgrad(W, IN, dcur, act(0), mlp.activation, e, 0);
 		if (enc_grad) launch_f32_layer_bwd(st, B, W, IN, params, dcur, act(0), mlp.activation, dnext);
 	}
-	if (dL_dinput) enc->backward_input(st, B, pos, dnext, dL_dinput, eparams, 2);
+	if (dL_dinput && lay.dL_dinput) {
+		dx_aos.reserve((size_t)B * n_input_dims * 4);
+		enc->backward_input(st, B, pos, dnext, dx_aos.as<float>(), eparams, 2);
+		launch_f32_transpose(st, B, n_input_dims, dx_aos.as<float>(), dL_dinput);
+	} else if (dL_dinput) {
+		enc->backward_input(st, B, pos, dnext, dL_dinput, eparams, 2);
+	}
 	if (dL_dparams && enc->n_params() > 0) enc->backward_params(st, B, pos, dnext, 2, dL_dparams + n_mlp);
 }
 

@@ -506,6 +506,16 @@ private:
 // least one hidden layer (fused_ok) runs the forward and the backward's delta chain as one register-resident launch
 // each (mlp_f32_fused.hip); CutlassMLP, and FullyFusedMLP without a hidden layer, run the layer kernels. Both give the
 // same bits. Sine (no backward from its forward value) is served by inference() only.
+//
+// Which matrices of a call are batch-contiguous (SoA: [width][B], the unpadded width, e.g. the output as
+// [n_output_dims][B]) instead of AoS rows ([B][padded width]). The bits of a mask are the C-ABI's (TCNN_LAYOUT_*).
+struct F32Layouts {
+	bool input = false, output = false, dL_doutput = false, dL_dinput = false;
+	F32Layouts() = default;
+	explicit F32Layouts(uint32_t mask) : input(mask & 1), output(mask & 2), dL_doutput(mask & 4), dL_dinput(mask & 8) {}
+	bool any() const { return input || output || dL_doutput || dL_dinput; }
+};
+
 struct NetworkF32Host {
 	EngineSwitches sw = EngineSwitches::from_env();
 	std::unique_ptr<EncodingHost> enc;
@@ -523,11 +533,20 @@ struct NetworkF32Host {
 	size_t keep_floats(uint32_t B) const {
 		return (size_t)B * ((size_t)mlp.n_input + (size_t)mlp.n_hidden_layers * mlp.width + mlp.padded_output);
 	}
-	// out32 fp32 [B][padded_output]; keep (nullable): keep_floats(B) floats, else two ping-pong buffers of the scratch
-	void forward(hipStream_t st, uint32_t B, const float* pos, const float* params, float* out32, float* keep);
-	// from a forward's keep: dL/dparams fp32 [n_params()] (nullable), dL/dinput fp32 [B][n_input_dims] (nullable)
+	// out32 fp32 [B][padded_output]; keep (nullable): keep_floats(B) floats, else two ping-pong buffers of the scratch.
+	// lay (fused_ok() only; the default is the launches of an AoS call, unchanged): pos as [n_input_dims][B], out32 as
+	// [n_output_dims][B]. The keep is AoS whatever lay says.
+	void forward(hipStream_t st, uint32_t B, const float* pos, const float* params, float* out32, float* keep, F32Layouts lay = {});
+	// from a forward's keep: dL/dparams fp32 [n_params()] (nullable), dL/dinput fp32 [B][n_input_dims] (nullable);
+	// lay as above: dout32 as [n_output_dims][B], dL_dinput as [n_input_dims][B]
 	void backward(hipStream_t st, uint32_t B, const float* pos, const float* params, const float* dout32, const float* keep,
-	              float* dL_dparams, float* dL_dinput);
+	              float* dL_dparams, float* dL_dinput, F32Layouts lay = {});
+	// A network alone whose Identity is the identity (scale 1, offset 0, no padding): a SoA input is the first layer's
+	// operand as it lies, and a SoA dL/dinput is the chain's D_0. Any other encoding keeps its AoS kernels behind a
+	// transpose of the positions / of dL/dinput (n_input_dims floats per row).
+	bool soa_first_layer() const;
+	const float* aos_positions(hipStream_t st, uint32_t B, const float* pos_soa);
+	DevBuf pos_aos, dy_aos, dx_aos;  // grow-only scratch of SoA calls
 	// Second order with respect to the input, from a forward's keep: dL_ddLdinput = dL2/d(dL/dinput) fp32
 	// [B][n_input_dims] -> dL2/dparams [n_params()], dL2/d(dL/doutput) [B][padded_output], dL2/dinput
 	// [B][n_input_dims] (each nullable, each overwritten). dout32, the first-order dL/doutput, may be null when only

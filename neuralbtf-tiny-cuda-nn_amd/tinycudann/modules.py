@@ -23,6 +23,7 @@ if not torch.cuda.is_available():
 
 PRECISION_FP32 = 0
 PRECISION_FP16 = 1
+LAYOUT_SOA = 15  # TCNN_LAYOUT_SOA_INPUT | _OUTPUT | _DL_DOUTPUT | _DL_DINPUT
 
 
 class _C:
@@ -200,6 +201,30 @@ class _NativeModule:
                                              _ptr(dL_dparams), _ptr(input), _ptr(output), _ptr(params)))
         return dL_dinput, dL_dparams
 
+    def fwd_soa(self, input, params, n_out):
+        """the forward on batch-contiguous matrices (tcnn_module_forward_layout, every layout bit set): input
+        [n_input_dims, B] -> output [n_out, B], n_out the unpadded n_output_dims"""
+        assert input.dtype == torch.float32 and input.is_contiguous() and input.shape[0] == self._n_in
+        assert params.dtype == self._param_dtype and params.numel() == self._n_params
+        B = input.shape[1]
+        out = torch.empty(n_out, B, dtype=self._out_dtype, device=input.device)
+        if not (input.requires_grad or params.requires_grad):
+            L.check(L.lib().tcnn_module_inference_layout(self.h, _stream(input), B, _ptr(input), _ptr(out), _ptr(params), LAYOUT_SOA))
+            return None, out
+        ctx = L.check_ptr(L.lib().tcnn_module_forward_layout(self.h, _stream(input), B, _ptr(input), _ptr(out), _ptr(params),
+                                                              int(input.requires_grad), LAYOUT_SOA))
+        return _NativeContext(ctx), out
+
+    def bwd_soa(self, ctx, input, params, output, dL_doutput, need_input, need_params):
+        """dL_doutput [n_out, B] -> dL_dinput [n_input_dims, B], dL_dparams"""
+        B = input.shape[1]
+        dL_dinput = torch.empty_like(input) if need_input else None
+        dL_dparams = torch.empty(self._n_params, dtype=self._param_dtype, device=input.device) if need_params else None
+        dL_doutput = dL_doutput.to(self._out_dtype).contiguous()
+        L.check(L.lib().tcnn_module_backward_layout(self.h, _stream(input), ctx.h, B, _ptr(dL_dinput), _ptr(dL_doutput),
+                                                    _ptr(dL_dparams), _ptr(input), _ptr(output), _ptr(params), LAYOUT_SOA))
+        return dL_dinput, dL_dparams
+
     def bwd_bwd_input(self, ctx, input, params, dL_ddLdinput, dL_doutput):
         """bindings.cpp:185-239: second-order gradients from dL/d(dL/dinput)."""
         B = input.shape[0]
@@ -301,6 +326,33 @@ class _module_function_backward(torch.autograd.Function):
         return None, doutput_grad, input_grad, params_grad, None
 
 
+class _module_function_soa(torch.autograd.Function):
+    """_module_function on batch-contiguous matrices (Module.forward(x, layout="soa")): first order only, a double
+    backward raises (once_differentiable)."""
+
+    @staticmethod
+    def forward(ctx, native_tcnn_module, input, params, loss_scale, n_out):
+        ctx.set_materialize_grads(False)
+        native_ctx, output = native_tcnn_module.fwd_soa(input, params, n_out)
+        ctx.save_for_backward(input, params, output)
+        ctx.native_tcnn_module = native_tcnn_module
+        ctx.native_ctx = native_ctx
+        ctx.loss_scale = loss_scale
+        return output
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, doutput):
+        if doutput is None:
+            return None, None, None, None, None
+        input, params, output = ctx.saved_tensors
+        input_grad, params_grad = ctx.native_tcnn_module.bwd_soa(
+            ctx.native_ctx, input, params, output, doutput.to(output.dtype) * ctx.loss_scale, ctx.needs_input_grad[1], ctx.needs_input_grad[2])
+        input_grad = None if input_grad is None else input_grad / ctx.loss_scale
+        params_grad = None if params_grad is None else params_grad / ctx.loss_scale
+        return None, input_grad, params_grad, None, None
+
+
 class Module(torch.nn.Module):
     def __init__(self, seed=1337):
         super().__init__()
@@ -312,7 +364,15 @@ class Module(torch.nn.Module):
         self.register_parameter(name="params", param=self.params)
         self.loss_scale = L.lib().tcnn_default_loss_scale(self.native_tcnn_module.param_precision())
 
-    def forward(self, x):
+    def forward(self, x, layout="aos"):
+        """layout="aos" (the default, the reference's call): x [B, n_input_dims] -> [B, n_output_dims].
+        layout="soa": batch-contiguous matrices, x [n_input_dims, B] -> [n_output_dims, B], and in the backward a
+        [n_output_dims, B] dL/doutput -> a [n_input_dims, B] dL/dinput, with no padded output columns anywhere. Served
+        by fp32 FullyFusedMLP network modules (dtype=torch.float32); first order only (a double backward raises)."""
+        if layout == "soa":
+            return self._forward_soa(x)
+        if layout != "aos":
+            raise ValueError(f"layout must be 'aos' or 'soa', got {layout!r}")
         if not x.is_cuda:
             warnings.warn("input must be a CUDA tensor, but isn't. This indicates suboptimal performance.")
             x = x.cuda()
@@ -337,6 +397,20 @@ class Module(torch.nn.Module):
         if batch_size == padded and output.shape[1] == self.n_output_dims:
             return output
         return output[:batch_size, :self.n_output_dims]
+
+    def _forward_soa(self, x):
+        if not x.is_cuda:
+            warnings.warn("input must be a CUDA tensor, but isn't. This indicates suboptimal performance.")
+            x = x.cuda()
+        batch_size = x.shape[1]
+        g = _granularity()
+        padded = (batch_size + g - 1) // g * g
+        if batch_size != padded:
+            x = torch.nn.functional.pad(x, [0, padded - batch_size])
+        x = x.to(torch.float).contiguous()
+        params = self.params.to(self.native_tcnn_module._param_dtype).contiguous()
+        output = _module_function_soa.apply(self.native_tcnn_module, x, params, self.loss_scale, self.n_output_dims)
+        return output if batch_size == padded else output[:, :batch_size]
 
     def __getstate__(self):
         """modules.py:194-199: pickle everything except the native module (a C-ABI handle)."""
