@@ -123,6 +123,19 @@ tcnn_context* tcnn_module_forward_layout(tcnn_module* m, void* stream, uint32_t 
 int tcnn_module_backward_layout(tcnn_module* m, void* stream, const tcnn_context* ctx, uint32_t n, float* dL_dinput,
                                 const void* dL_doutput, void* dL_dparams, const float* input, const void* output,
                                 const void* params, uint32_t layouts);
+/* Value and input Jacobian at inference in one forward-mode launch (beyond the reference): output as
+ * tcnn_module_inference writes it, to the bit, and jacobian[b][o][d] = d output_o / d input_d, fp32
+ * [n][n_output_dims][n_input_dims] with n_output_dims the (unpadded) width the module was created with. Nothing is
+ * kept and no context is made. `layouts` takes TCNN_LAYOUT_SOA_INPUT (input [n_input_dims][n]) and
+ * TCNN_LAYOUT_SOA_OUTPUT (output [n_output_dims][n] and jacobian [n_output_dims * n_input_dims][n], row
+ * o * n_input_dims + d); each result is the AoS call's to the bit, transposed. n: a multiple of 128.
+ * Served by Fp32 network modules whose network is FullyFusedMLP with at least one hidden layer, created alone or
+ * behind a lone Identity encoding (any scale / offset), with every activation but Sine. Any other module answers
+ * "<name>[ behind <encoding>]: inference_jacobian is not implemented by the MI355X engine yet (fp32 FullyFusedMLP
+ * network modules alone or behind a lone Identity encoding only)"; Sine answers that it has no backward from its
+ * forward value. */
+int tcnn_module_inference_jacobian(tcnn_module* m, void* stream, uint32_t n, const float* input, void* output, float* jacobian,
+                                   const void* params, uint32_t layouts);
 /* The torch binding's backward with its loss-scale arithmetic folded in (reference
  * bindings/torch/tinycudann/modules.py:128-138): dL_doutput (fp16) is multiplied by loss_scale and
  * rounded to fp16, the module's backward runs on it, dL_dinput (fp32) is divided by loss_scale and

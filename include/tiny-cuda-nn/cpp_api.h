@@ -88,6 +88,13 @@ public:
 	                                     const float* input, const void* dL_doutput, void* dL_dparams, void* dL_ddLdoutput,
 	                                     float* dL_dinput, const void* params) = 0;
 
+	// Beyond the reference: the output and jacobian[b][o][d] = d output_o / d input_d in one launch, nothing kept
+	// (tcnn_module_inference_jacobian; layouts: TCNN_LAYOUT_SOA_INPUT | TCNN_LAYOUT_SOA_OUTPUT). Fp32 FullyFusedMLP
+	// network modules alone or behind a lone Identity encoding; any other module throws.
+	virtual void inference_jacobian(hipStream_t, uint32_t, const float*, void*, float*, const void*, uint32_t = 0) {
+		throw std::runtime_error(name() + ": inference_jacobian is not implemented");
+	}
+
 	virtual uint32_t n_input_dims() const = 0;
 	virtual uint32_t n_output_dims() const = 0;
 	Precision output_precision() const { return m_output_precision; }
@@ -131,6 +138,10 @@ public:
 	                             const void* params) override {
 		check(tcnn_module_backward_backward_input(m_h, stream, native(ctx), n, dL_ddLdinput, input, dL_doutput, dL_dparams,
 		                                          dL_ddLdoutput, dL_dinput, params));
+	}
+	void inference_jacobian(hipStream_t stream, uint32_t n, const float* input, void* output, float* jacobian, const void* params,
+	                        uint32_t layouts = 0) override {
+		check(tcnn_module_inference_jacobian(m_h, stream, n, input, output, jacobian, params, layouts));
 	}
 	uint32_t n_input_dims() const override { return tcnn_module_n_input_dims(m_h); }
 	uint32_t n_output_dims() const override { return tcnn_module_n_output_dims(m_h); }

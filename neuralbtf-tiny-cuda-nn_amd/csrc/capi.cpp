@@ -123,6 +123,14 @@ struct ModuleBase {
 	                             uint32_t) {
 		refuse_layouts();
 	}
+	// Value and input Jacobian in one launch (tcnn_module_inference_jacobian): only an fp32 FullyFusedMLP network module
+	// behind a lone Identity serves it; `front` names what stands in front of the network, when that is the obstacle
+	void refuse_jacobian(const std::string& front = "") const {
+		throw std::runtime_error(name() + (front.empty() ? "" : " behind " + front) +
+		                         ": inference_jacobian is not implemented by the MI355X engine yet (fp32 FullyFusedMLP network modules "
+		                         "alone or behind a lone Identity encoding only)");
+	}
+	virtual void inference_jacobian(hipStream_t, uint32_t, const float*, void*, float*, const void*, uint32_t) { refuse_jacobian(); }
 	virtual GridEncodingHost* grid_encoding() { return nullptr; }
 	// precision of the parameters, the output, dL/doutput and dL/dparams (TCNN_PRECISION_*): fp16 for
 	// every module but an encoding or a network created with Fp32
@@ -322,6 +330,20 @@ struct ModuleNWIEF32 : ModuleBase {
 		TCNN_CHECK(params && in && dL_ddLdin, "backward_backward_input needs the input, the parameters and dL_ddLdinput");
 		model.backward_backward_input(st, n, in, (const float*)params, dL_ddLdin, (const float*)dL_dout, kept(st, ctx, n, in, params),
 		                              (float*)dL_dparams, (float*)dL_ddLdout, dL_din);
+	}
+	// f(x) and df/dx at inference, one forward-mode launch with nothing kept (beyond the reference). mask: the input and
+	// output bits of the layout calls; the Jacobian follows the output bit. Batches of 128 (the kernel's granule).
+	void inference_jacobian(hipStream_t st, uint32_t n, const float* in, void* out, float* jac, const void* params, uint32_t mask) override {
+		TCNN_CHECK(mask < 4, "inference_jacobian: layouts takes TCNN_LAYOUT_SOA_INPUT and TCNN_LAYOUT_SOA_OUTPUT only");
+		if (!model.fused_ok()) refuse_jacobian();
+		const EncodingHost::Part* lone = model.enc->lone_part();
+		if (!lone || lone->kind != COMP_IDENTITY) refuse_jacobian(model.enc->name());
+		TCNN_CHECK(!model.has_sine(), name() + ": Sine has no backward from its forward value: inference_jacobian serves the other eight "
+		                                       "activations (use inference for the value)");
+		TCNN_CHECK(n % 128 == 0, "inference_jacobian: batch size must be a multiple of 128");
+		if (!n) return;
+		TCNN_CHECK(in && out && jac && params, "inference_jacobian needs the input, the output, the Jacobian and the parameters");
+		model.jacobian(st, n, in, (const float*)params, (float*)out, jac, F32Layouts(mask));
 	}
 	GridEncodingHost* grid_encoding() override { return model.enc->lone_grid(); }
 	// "fused" / "chain": the whole network in one launch (mlp_f32_fused.hip); the weight gradients stay per layer
@@ -570,6 +592,15 @@ int tcnn_module_backward(tcnn_module* m, void* stream, const tcnn_context* ctx, 
 int tcnn_module_inference_layout(tcnn_module* m, void* stream, uint32_t n, const float* in, void* out, const void* params, uint32_t layouts) {
 	if (!layouts) return tcnn_module_inference(m, stream, n, in, out, params);
 	return guard([&] { m->m->inference_layout((hipStream_t)stream, n, in, out, params, layouts); });
+}
+
+int tcnn_module_inference_jacobian(tcnn_module* m, void* stream, uint32_t n, const float* in, void* out, float* jacobian, const void* params,
+                                   uint32_t layouts) {
+	return guard([&] {
+		TCNN_CHECK(m && m->m, "inference_jacobian: null module");
+		// an empty batch still answers for the module: a refusal does not depend on n
+		m->m->inference_jacobian((hipStream_t)stream, n, in, out, jacobian, params, layouts);
+	});
 }
 
 tcnn_context* tcnn_module_forward_layout(tcnn_module* m, void* stream, uint32_t n, const float* in, void* out, const void* params, int prep,

@@ -493,6 +493,13 @@ void launch_f32_mlp_fwd_layout(hipStream_t st, uint32_t B, uint32_t IN, uint32_t
 void launch_f32_mlp_bwd_chain_layout(hipStream_t st, uint32_t B, uint32_t IN, uint32_t W, uint32_t NH, uint32_t OUTP, uint32_t n_out,
                                      const float* params, const float* dy, bool dy_soa, float* dy_aos, const float* keep, float* d_hidden,
                                      float* d0, bool d0_soa, int act, int out_act);
+// Value and input Jacobian of the same network behind an Identity encoding, in one forward-mode launch
+// (mlp_f32_jacobian.hip): x the caller's D inputs per sample ([B][D], or [D][B] when x_soa), the encoded row being
+// x scale + offset then ones up to IN. y [B][OUTP] with the bits of launch_f32_mlp_fwd, jac[b][o][d] = dy_o / dx_d
+// [B][n_out][D]; y_soa: y [n_out][B] and jac [n_out D][B] (row o D + d). Nothing past n_out or D is stored.
+void launch_f32_mlp_jacobian(hipStream_t st, uint32_t B, uint32_t D, uint32_t IN, uint32_t W, uint32_t NH, uint32_t OUTP, uint32_t n_out,
+                             const float* params, const float* x, bool x_soa, float scale, float offset, float* y, float* jac, bool y_soa,
+                             int act, int out_act);
 // dst[C][R] = src[R][C]^T
 void launch_f32_transpose(hipStream_t st, uint32_t R, uint32_t C, const float* src, float* dst);
 

@@ -1305,6 +1305,18 @@ bool NetworkF32Host::soa_first_layer() const {
 	return p && p->kind == COMP_IDENTITY && p->f0 == 1.0f && p->f1 == 0.0f && p->width == p->n_values;
 }
 
+bool NetworkF32Host::jacobian_ok() const {
+	const EncodingHost::Part* p = enc->lone_part();
+	return fused_ok() && !has_sine() && p && p->kind == COMP_IDENTITY;
+}
+
+void NetworkF32Host::jacobian(hipStream_t st, uint32_t B, const float* x, const float* params, float* y, float* J, F32Layouts lay) {
+	TCNN_CHECK(jacobian_ok(), "fp32 network: the input Jacobian needs the fused kernels (FullyFusedMLP) behind a lone Identity, without Sine");
+	const EncodingHost::Part* p = enc->lone_part();
+	launch_f32_mlp_jacobian(st, B, n_input_dims, mlp.n_input, mlp.width, mlp.n_hidden_layers, mlp.padded_output, n_output_dims, params, x,
+	                        lay.input, p->f0, p->f1, y, J, lay.output, mlp.activation, mlp.output_activation);
+}
+
 const float* NetworkF32Host::aos_positions(hipStream_t st, uint32_t B, const float* pos_soa) {
 	pos_aos.reserve((size_t)B * n_input_dims * 4);
 	launch_f32_transpose(st, n_input_dims, B, pos_soa, pos_aos.as<float>());

@@ -545,6 +545,12 @@ struct NetworkF32Host {
 	// operand as it lies, and a SoA dL/dinput is the chain's D_0. Any other encoding keeps its AoS kernels behind a
 	// transpose of the positions / of dL/dinput (n_input_dims floats per row).
 	bool soa_first_layer() const;
+	// Value and input Jacobian at inference, one forward-mode launch (mlp_f32_jacobian.hip), nothing kept: x [B][D]
+	// (lay.input: [D][B]), D = n_input_dims -> y [B][padded_output] with forward()'s bits and J[b][o][d] = dy_o / dx_d,
+	// [B][n_output_dims][D]; lay.output: y [n_output_dims][B] and J [n_output_dims D][B], row o D + d. B a multiple of
+	// 128. Served when jacobian_ok(): fused_ok() behind a lone Identity (any scale / offset), no Sine.
+	bool jacobian_ok() const;
+	void jacobian(hipStream_t st, uint32_t B, const float* x, const float* params, float* y, float* J, F32Layouts lay = {});
 	const float* aos_positions(hipStream_t st, uint32_t B, const float* pos_soa);
 	DevBuf pos_aos, dy_aos, dx_aos;  // grow-only scratch of SoA calls
 	// Second order with respect to the input, from a forward's keep: dL_ddLdinput = dL2/d(dL/dinput) fp32

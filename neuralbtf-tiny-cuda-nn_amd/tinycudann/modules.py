@@ -225,6 +225,18 @@ class _NativeModule:
                                                     _ptr(dL_dparams), _ptr(input), _ptr(output), _ptr(params), LAYOUT_SOA))
         return dL_dinput, dL_dparams
 
+    def jacobian(self, input, params, n_out, soa):
+        """tcnn_module_inference_jacobian: input [B, D] -> (output [B, padded n_out], J [B, n_out, D]); soa: input
+        [D, B] -> (output [n_out, B], J [n_out, D, B])"""
+        assert input.dtype == torch.float32 and input.is_contiguous() and input.shape[0 if soa else 1] == self._n_in
+        assert params.dtype == self._param_dtype and params.numel() == self._n_params
+        B, D, dev = input.shape[1 if soa else 0], self._n_in, input.device
+        out = torch.empty((n_out, B) if soa else (B, self._n_out), dtype=self._out_dtype, device=dev)
+        jac = torch.empty((n_out, D, B) if soa else (B, n_out, D), dtype=torch.float32, device=dev)
+        L.check(L.lib().tcnn_module_inference_jacobian(self.h, _stream(input), B, _ptr(input), _ptr(out), _ptr(jac), _ptr(params),
+                                                       3 if soa else 0))
+        return out, jac
+
     def bwd_bwd_input(self, ctx, input, params, dL_ddLdinput, dL_doutput):
         """bindings.cpp:185-239: second-order gradients from dL/d(dL/dinput)."""
         B = input.shape[0]
@@ -411,6 +423,33 @@ class Module(torch.nn.Module):
         params = self.params.to(self.native_tcnn_module._param_dtype).contiguous()
         output = _module_function_soa.apply(self.native_tcnn_module, x, params, self.loss_scale, self.n_output_dims)
         return output if batch_size == padded else output[:, :batch_size]
+
+    def value_and_jacobian(self, x, layout="aos"):
+        """f(x) and its input Jacobian at inference, in one forward-mode launch that keeps nothing:
+        layout="aos": x [B, n_input_dims] -> (y [B, n_output_dims], J [B, n_output_dims, n_input_dims]);
+        layout="soa": x [n_input_dims, B] -> (y [n_output_dims, B], J [n_output_dims, n_input_dims, B]),
+        with J[b, o, d] = dy_o / dx_d and y the bits forward(x) returns. Inference only: no autograd graph is recorded,
+        the results do not require grad and gradients do not flow through this call to x or to the parameters (use
+        forward and autograd.grad for that). Served by fp32 FullyFusedMLP modules (dtype=torch.float32): a Network, or
+        a NetworkWithInputEncoding behind a lone Identity encoding; every activation but Sine."""
+        if layout not in ("aos", "soa"):
+            raise ValueError(f"layout must be 'aos' or 'soa', got {layout!r}")
+        soa = layout == "soa"
+        with torch.no_grad():
+            if not x.is_cuda:
+                warnings.warn("input must be a CUDA tensor, but isn't. This indicates suboptimal performance.")
+                x = x.cuda()
+            batch_size = x.shape[1 if soa else 0]
+            g = _granularity()
+            padded = (batch_size + g - 1) // g * g
+            if batch_size != padded:
+                x = torch.nn.functional.pad(x, [0, padded - batch_size] if soa else [0, 0, 0, padded - batch_size])
+            x = x.to(torch.float).contiguous()
+            params = self.params.detach().to(self.native_tcnn_module._param_dtype).contiguous()
+            y, jac = self.native_tcnn_module.jacobian(x, params, self.n_output_dims, soa)
+            if soa:
+                return (y, jac) if batch_size == padded else (y[:, :batch_size], jac[:, :, :batch_size])
+            return y[:batch_size, :self.n_output_dims], jac[:batch_size]
 
     def __getstate__(self):
         """modules.py:194-199: pickle everything except the native module (a C-ABI handle)."""
