@@ -136,6 +136,23 @@ int tcnn_module_backward_layout(tcnn_module* m, void* stream, const tcnn_context
  * forward value. */
 int tcnn_module_inference_jacobian(tcnn_module* m, void* stream, uint32_t n, const float* input, void* output, float* jacobian,
                                    const void* params, uint32_t layouts);
+/* Value and directional input derivatives (Jacobian-vector products) at inference in one forward-mode launch (beyond
+ * the reference): output as tcnn_module_inference_jacobian writes it, and
+ * jvp[b][o][k] = sum_d (d output_o / d input_d) directions[b][k][d], fp32 [n][n_output_dims][n_directions], for
+ * directions fp32 [n][n_directions][n_input_dims]. directions == NULL means the n_input_dims unit vectors: n_directions
+ * must then be 0 or n_input_dims and jvp is the Jacobian [n][n_output_dims][n_input_dims]. Nothing is kept.
+ * TCNN_LAYOUT_SOA_INPUT governs input and directions together (directions [n_directions * n_input_dims][n], row
+ * k * n_input_dims + d); under TCNN_LAYOUT_SOA_OUTPUT jvp is [n_output_dims * n_directions][n], row
+ * o * n_directions + k. Each result is the AoS call's to the bit, transposed. n: a multiple of 128.
+ * Served by the modules tcnn_module_inference_jacobian serves (with NULL directions: its bits) and by the same networks
+ * behind a lone grid encoding (HashGrid / DenseGrid / TiledGrid, every hash and interpolation; Nearest gives exact
+ * zeros) of 2 or 3 input dimensions, 2, 4 or 8 features per level and an encoded width of at most 64 columns, with
+ * neither max_level nor stochastic interpolation in effect. Any other module answers "<name>[ behind <encoding>]:
+ * inference_jvp is not implemented by the MI355X engine yet (fp32 FullyFusedMLP network modules alone, behind a lone
+ * Identity encoding or behind a lone grid encoding only)[: <what about the grid is not served>]"; Sine answers that it
+ * has no backward from its forward value. */
+int tcnn_module_inference_jvp(tcnn_module* m, void* stream, uint32_t n, const float* input, const float* directions,
+                              uint32_t n_directions, void* output, float* jvp, const void* params, uint32_t layouts);
 /* The torch binding's backward with its loss-scale arithmetic folded in (reference
  * bindings/torch/tinycudann/modules.py:128-138): dL_doutput (fp16) is multiplied by loss_scale and
  * rounded to fp16, the module's backward runs on it, dL_dinput (fp32) is divided by loss_scale and

@@ -94,6 +94,12 @@ public:
 	virtual void inference_jacobian(hipStream_t, uint32_t, const float*, void*, float*, const void*, uint32_t = 0) {
 		throw std::runtime_error(name() + ": inference_jacobian is not implemented");
 	}
+	// Beyond the reference: the output and jvp[b][o][k] = sum_d d output_o / d input_d directions[b][k][d] in one
+	// launch, nothing kept (tcnn_module_inference_jvp); null directions are the unit vectors. What inference_jacobian
+	// serves, and the same networks behind a lone grid encoding; any other module throws.
+	virtual void inference_jvp(hipStream_t, uint32_t, const float*, const float*, uint32_t, void*, float*, const void*, uint32_t = 0) {
+		throw std::runtime_error(name() + ": inference_jvp is not implemented");
+	}
 
 	virtual uint32_t n_input_dims() const = 0;
 	virtual uint32_t n_output_dims() const = 0;
@@ -142,6 +148,10 @@ public:
 	void inference_jacobian(hipStream_t stream, uint32_t n, const float* input, void* output, float* jacobian, const void* params,
 	                        uint32_t layouts = 0) override {
 		check(tcnn_module_inference_jacobian(m_h, stream, n, input, output, jacobian, params, layouts));
+	}
+	void inference_jvp(hipStream_t stream, uint32_t n, const float* input, const float* directions, uint32_t n_directions, void* output,
+	                   float* jvp, const void* params, uint32_t layouts = 0) override {
+		check(tcnn_module_inference_jvp(m_h, stream, n, input, directions, n_directions, output, jvp, params, layouts));
 	}
 	uint32_t n_input_dims() const override { return tcnn_module_n_input_dims(m_h); }
 	uint32_t n_output_dims() const override { return tcnn_module_n_output_dims(m_h); }

@@ -131,6 +131,14 @@ struct ModuleBase {
 		                         "alone or behind a lone Identity encoding only)");
 	}
 	virtual void inference_jacobian(hipStream_t, uint32_t, const float*, void*, float*, const void*, uint32_t) { refuse_jacobian(); }
+	// Value and Jacobian-vector products in one launch (tcnn_module_inference_jvp): an fp32 FullyFusedMLP network module
+	// alone, behind a lone Identity or behind a lone grid; `front` as above, `why` what about it is not served
+	void refuse_jvp(const std::string& front = "", const std::string& why = "") const {
+		throw std::runtime_error(name() + (front.empty() ? "" : " behind " + front) +
+		                         ": inference_jvp is not implemented by the MI355X engine yet (fp32 FullyFusedMLP network modules alone, "
+		                         "behind a lone Identity encoding or behind a lone grid encoding only)" + (why.empty() ? "" : ": " + why));
+	}
+	virtual void inference_jvp(hipStream_t, uint32_t, const float*, const float*, uint32_t, void*, float*, const void*, uint32_t) { refuse_jvp(); }
 	virtual GridEncodingHost* grid_encoding() { return nullptr; }
 	// precision of the parameters, the output, dL/doutput and dL/dparams (TCNN_PRECISION_*): fp16 for
 	// every module but an encoding or a network created with Fp32
@@ -344,6 +352,26 @@ struct ModuleNWIEF32 : ModuleBase {
 		if (!n) return;
 		TCNN_CHECK(in && out && jac && params, "inference_jacobian needs the input, the output, the Jacobian and the parameters");
 		model.jacobian(st, n, in, (const float*)params, (float*)out, jac, F32Layouts(mask));
+	}
+	// f(x) and J(x) v_k for K directions per sample, one forward-mode launch with nothing kept (beyond the reference);
+	// null directions are the unit vectors. mask as inference_jacobian: the input bit governs the directions too, the
+	// product follows the output bit.
+	void inference_jvp(hipStream_t st, uint32_t n, const float* in, const float* directions, uint32_t n_directions, void* out, float* jvp,
+	                   const void* params, uint32_t mask) override {
+		TCNN_CHECK(mask < 4, "inference_jvp: layouts takes TCNN_LAYOUT_SOA_INPUT and TCNN_LAYOUT_SOA_OUTPUT only");
+		if (!model.fused_ok()) refuse_jvp();
+		const EncodingHost::Part* lone = model.enc->lone_part();
+		if (!lone || (lone->kind != COMP_IDENTITY && lone->kind != COMP_GRID)) refuse_jvp(model.enc->name());
+		TCNN_CHECK(!model.has_sine(), name() + ": Sine has no backward from its forward value: inference_jvp serves the other eight "
+		                                       "activations (use inference for the value)");
+		const std::string why = model.jvp_refusal();
+		if (!why.empty()) refuse_jvp(model.enc->name(), why);
+		TCNN_CHECK(n % 128 == 0, "inference_jvp: batch size must be a multiple of 128");
+		TCNN_CHECK(directions ? n_directions >= 1 : (n_directions == 0 || n_directions == model.n_input_dims),
+		           "inference_jvp: n_directions must be at least 1, or 0 or the input width with null directions (the unit vectors)");
+		if (!n) return;
+		TCNN_CHECK(in && out && jvp && params, "inference_jvp needs the input, the output, the product and the parameters");
+		model.jvp(st, n, in, directions, n_directions, (const float*)params, (float*)out, jvp, F32Layouts(mask));
 	}
 	GridEncodingHost* grid_encoding() override { return model.enc->lone_grid(); }
 	// "fused" / "chain": the whole network in one launch (mlp_f32_fused.hip); the weight gradients stay per layer
@@ -600,6 +628,15 @@ int tcnn_module_inference_jacobian(tcnn_module* m, void* stream, uint32_t n, con
 		TCNN_CHECK(m && m->m, "inference_jacobian: null module");
 		// an empty batch still answers for the module: a refusal does not depend on n
 		m->m->inference_jacobian((hipStream_t)stream, n, in, out, jacobian, params, layouts);
+	});
+}
+
+int tcnn_module_inference_jvp(tcnn_module* m, void* stream, uint32_t n, const float* in, const float* directions, uint32_t n_directions,
+                              void* out, float* jvp, const void* params, uint32_t layouts) {
+	return guard([&] {
+		TCNN_CHECK(m && m->m, "inference_jvp: null module");
+		// an empty batch still answers for the module: a refusal does not depend on n
+		m->m->inference_jvp((hipStream_t)stream, n, in, directions, n_directions, out, jvp, params, layouts);
 	});
 }
 

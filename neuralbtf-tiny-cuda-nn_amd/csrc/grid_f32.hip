@@ -4,7 +4,7 @@
 //   k_grid_bwd_lds_f32  fp32 dL/dy (AoS) -> per-chunk fp32 gradient slabs, LDS-privatised int32 sums
 // Nothing here is narrowed to fp16: table entries, corner weights, dL/dy and the output stay fp32.
 // The index arithmetic is grid_device.h's (pos_fract, grid_index, the reference's corner order), so
-// the entries touched are those of the fp16 kernels. dL/dinput and the second-order kernels are the
+// the entries touched are those of the fp16 kernels; one level of one point is grid_f32_device.h's. dL/dinput and the second-order kernels are the
 // typed k_grid_bwd_input / k_grid_bwd_bwd of grid.hip.
 #include "kernels.h"
 
@@ -13,60 +13,9 @@
 #include "grid_bwd_lds.h"
 #include "grid_device.h"
 #include "grid_dispatch.h"
+#include "grid_f32_device.h"
 
 namespace tcnn_amd {
-
-// F fp32 features of one table entry / one point-level: one dwordx2 (F = 2), dwordx4 (F = 4) or two
-// dwordx4 (F = 8) where the address allows
-template <uint32_t F>
-struct alignas(F * 4 > 16 ? 16 : F * 4) FVec { float v[F]; };
-
-template <uint32_t F>
-__device__ __forceinline__ FVec<F> load_fvec(const float* __restrict__ p, bool vec) {
-	if (vec) return *(const FVec<F>*)p;
-	FVec<F> r;
-#pragma unroll
-	for (uint32_t f = 0; f < F; ++f) r.v[f] = p[f];
-	return r;
-}
-
-// One level of one point (reference kernel_grid with T = float, grid.h:93-168): fp32 weight products in
-// the reference's order and one fp32 FMA per corner and feature, corners in the reference's order.
-template <uint32_t D, uint32_t F, HashType H>
-__device__ __forceinline__ void encode_level_f32(const float* __restrict__ table, const LevelInfo& li, bool hash_grid, Interp interp,
-                                                 const float* x, bool vec, float* r) {
-	float p[D];
-	uint32_t pg[D];
-#pragma unroll
-	for (uint32_t d = 0; d < D; ++d) pos_fract(x[d], li.scale, interp, p[d], pg[d]);
-	if (interp == Interp::Nearest) {
-		const FVec<F> v = load_fvec<F>(table + (size_t)(li.offset + grid_index<D, H>(hash_grid, li.size, li.res, pg)) * F, vec);
-#pragma unroll
-		for (uint32_t f = 0; f < F; ++f) r[f] = v.v[f];
-		return;
-	}
-	constexpr uint32_t NC = 1u << D;
-	FVec<F> v[NC];
-	float w[NC];
-#pragma unroll
-	for (uint32_t c = 0; c < NC; ++c) {  // every gather issued before the FMA chain consumes one
-		float wc = 1.0f;
-		uint32_t local[D];
-#pragma unroll
-		for (uint32_t d = 0; d < D; ++d) {
-			if ((c & (1u << d)) == 0) { wc *= 1.0f - p[d]; local[d] = pg[d]; }
-			else { wc *= p[d]; local[d] = pg[d] + 1; }
-		}
-		w[c] = wc;
-		v[c] = load_fvec<F>(table + (size_t)(li.offset + grid_index<D, H>(hash_grid, li.size, li.res, local)) * F, vec);
-	}
-#pragma unroll
-	for (uint32_t f = 0; f < F; ++f) r[f] = 0.0f;
-#pragma unroll
-	for (uint32_t c = 0; c < NC; ++c)
-#pragma unroll
-		for (uint32_t f = 0; f < F; ++f) r[f] = __builtin_fmaf(w[c], v[c].v[f], r[f]);
-}
 
 // AoS forward: one thread per point and group of G consecutive levels, G * F >= 4 features, so a thread
 // writes 16 contiguous bytes of its row (32 for F = 8) in dwordx4 stores and consecutive threads write

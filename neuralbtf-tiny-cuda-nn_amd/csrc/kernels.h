@@ -500,6 +500,16 @@ void launch_f32_mlp_bwd_chain_layout(hipStream_t st, uint32_t B, uint32_t IN, ui
 void launch_f32_mlp_jacobian(hipStream_t st, uint32_t B, uint32_t D, uint32_t IN, uint32_t W, uint32_t NH, uint32_t OUTP, uint32_t n_out,
                              const float* params, const float* x, bool x_soa, float scale, float offset, float* y, float* jac, bool y_soa,
                              int act, int out_act);
+// Value and n_directions directional input derivatives of the same network behind a lone grid, or behind an Identity
+// row as above (grid null; table unused), in one forward-mode launch that keeps nothing (mlp_f32_jvp.hip). directions
+// [B][K][D] ([K D][B] when x_soa, like x); null: the D unit vectors, n_directions = D, and jvp is the Jacobian.
+// y as launch_f32_mlp_jacobian writes it, jvp[b][o][k] = sum_d dy_o / dx_d v[b][k][d], [B][n_out][K]; y_soa:
+// [n_out K][B] (row o K + k). table: the grid's fp32 entries. Nothing past n_out or K is stored.
+// A grid in front is served when f32_mlp_jvp_grid_ok: 2 or 3 input dimensions, 2, 4 or 8 features per level, IN <= 64.
+bool f32_mlp_jvp_grid_ok(uint32_t D, uint32_t F, uint32_t IN);
+void launch_f32_mlp_jvp(hipStream_t st, uint32_t B, uint32_t D, uint32_t IN, uint32_t W, uint32_t NH, uint32_t OUTP, uint32_t n_out,
+                        const float* params, const float* x, const float* directions, uint32_t n_directions, bool x_soa, float* y, float* jvp,
+                        bool y_soa, int act, int out_act, const GridCall* grid, const float* table, float scale, float offset);
 // dst[C][R] = src[R][C]^T
 void launch_f32_transpose(hipStream_t st, uint32_t R, uint32_t C, const float* src, float* dst);
 

@@ -26,50 +26,11 @@
 // with J [B][n_out][D], or SoA [n_out][B] with J [n_out D][B] (row o D + d). For a fixed neuron the 16 lanes of a
 // quarter hold 16 consecutive batch rows, so every SoA access covers 64-byte runs. J exists only for o < n_out and
 // d < D: nothing past those is stored.
-#include "mlp_f32_ops.h"
+#include "mlp_f32_chain.h"
 
 namespace tcnn_amd {
 
 namespace {
-
-constexpr uint32_t JAC_ROWS_PER_WAVE = 16, JAC_ROWS_PER_BLOCK = 64;
-
-// acc[i][c] += W[16 c + r][16 s + 4 q + j] x[i][s][j] for the value (i = 0) and the TG tangents, the first nct of NC
-// column tiles; wp = &W[r][4 q] of the first tile, K = 16 WT the row length of W. The value's order is
-// fwd_from_regs' (mlp_f32_fused.hip).
-template <int WT, int NQ, int NC>
-__device__ __forceinline__ void jac_from_regs(const float* __restrict__ wp, uint32_t nct, const f4 (&x)[NQ][WT], f4 (&acc)[NQ][NC]) {
-	constexpr uint32_t K = 16 * WT;
-#pragma unroll
-	for (int s = 0; s < WT; ++s)
-#pragma unroll
-		for (int c = 0; c < NC; ++c) {
-			if ((uint32_t)c < nct) {
-				const f4 w = *(const f4*)(wp + (size_t)c * 16 * K + 16 * s);
-#pragma unroll
-				for (int j = 0; j < 4; ++j)
-#pragma unroll
-					for (int i = 0; i < NQ; ++i) acc[i][c] = mfma4(w[j], x[i][s][j], acc[i][c]);
-			}
-		}
-}
-
-// h <- act(h) and T_d <- act'(h) o T_d, the factor from the post-activation value through the delta chain's function
-// (bwd_act with a unit delta is the factor itself)
-template <int WT, int NQ>
-__device__ __forceinline__ void jac_activate(f4 (&h)[NQ][WT], int act) {
-	if (act == ACT_NONE) return;
-#pragma unroll
-	for (int c = 0; c < WT; ++c)
-#pragma unroll
-		for (int e = 0; e < 4; ++e) {
-			const float y = fwd_act(act, h[0][c][e]);
-			const float f = bwd_act(act, 1.0f, y);
-			h[0][c][e] = y;
-#pragma unroll
-			for (int i = 1; i < NQ; ++i) h[i][c][e] *= f;
-		}
-}
 
 // P = [W0 [W][IN] | W1 .. W_{NH-1} [W][W] | Wout [OUTP][W]]; X the caller's inputs, D of them per sample, the Identity
 // row being x scale + offset then ones up to IN. Y and J as above. Grid B / 64.

@@ -1317,6 +1317,35 @@ void NetworkF32Host::jacobian(hipStream_t st, uint32_t B, const float* x, const 
 	                        lay.input, p->f0, p->f1, y, J, lay.output, mlp.activation, mlp.output_activation);
 }
 
+std::string NetworkF32Host::jvp_refusal() const {
+	const EncodingHost::Part* p = enc->lone_part();
+	if (!fused_ok()) return "the network is not a FullyFusedMLP of width 16, 32, 64 or 128 with a hidden layer";
+	if (has_sine()) return "Sine has no backward from its forward value";
+	if (!p || (p->kind != COMP_IDENTITY && p->kind != COMP_GRID)) return "neither an Identity nor a grid stands alone in front";
+	if (p->kind == COMP_IDENTITY) return "";
+	const GridEncodingHost& g = *p->grid;
+	const uint32_t D = g.desc.n_pos_dims, F = g.desc.n_features_per_level;
+	if (D != 2 && D != 3) return "a grid of " + std::to_string(D) + " input dimensions (2 or 3 are served)";
+	if (F != 2 && F != 4 && F != 8) return "a grid of " + std::to_string(F) + " features per level (2, 4 or 8 are served)";
+	if (!f32_mlp_jvp_grid_ok(D, F, mlp.n_input)) return "an encoded width of " + std::to_string(mlp.n_input) + " (at most 64 is served)";
+	if (g.opts().active) return "a grid with max_level or stochastic interpolation in effect";
+	return "";
+}
+
+void NetworkF32Host::jvp(hipStream_t st, uint32_t B, const float* x, const float* directions, uint32_t n_directions, const float* params,
+                         float* y, float* Jv, F32Layouts lay) {
+	const std::string why = jvp_refusal();
+	TCNN_CHECK(why.empty(), "fp32 network: no Jacobian-vector product: " + why);
+	TCNN_CHECK(directions || n_directions == 0 || n_directions == n_input_dims,
+	           "fp32 network: null directions are the unit vectors: n_directions must be 0 or the input width");
+	const uint32_t K = directions ? n_directions : n_input_dims;
+	const EncodingHost::Part* p = enc->lone_part();
+	const GridCall gc = p->grid ? p->grid->call() : GridCall{};
+	launch_f32_mlp_jvp(st, B, n_input_dims, mlp.n_input, mlp.width, mlp.n_hidden_layers, mlp.padded_output, n_output_dims, params, x, directions,
+	                   K, lay.input, y, Jv, lay.output, mlp.activation, mlp.output_activation, p->grid ? &gc : nullptr,
+	                   p->grid ? params + mlp.n_params() + p->param_offset : nullptr, p->f0, p->f1);
+}
+
 const float* NetworkF32Host::aos_positions(hipStream_t st, uint32_t B, const float* pos_soa) {
 	pos_aos.reserve((size_t)B * n_input_dims * 4);
 	launch_f32_transpose(st, n_input_dims, B, pos_soa, pos_aos.as<float>());

@@ -551,6 +551,16 @@ struct NetworkF32Host {
 	// 128. Served when jacobian_ok(): fused_ok() behind a lone Identity (any scale / offset), no Sine.
 	bool jacobian_ok() const;
 	void jacobian(hipStream_t st, uint32_t B, const float* x, const float* params, float* y, float* J, F32Layouts lay = {});
+	// Value and K = n_directions directional input derivatives at inference, one forward-mode launch (mlp_f32_jvp.hip),
+	// nothing kept: directions v [B][K][D] (lay.input: [K D][B], like x) -> y as jacobian() writes it and
+	// Jv[b][o][k] = sum_d dy_o / dx_d v[b][k][d], [B][n_output_dims][K]; lay.output: [n_output_dims K][B], row o K + k.
+	// Null directions are the D unit vectors (n_directions 0 or D) and Jv is the Jacobian; behind an Identity it then
+	// carries jacobian()'s bits. Served when jvp_refusal() is empty: what jacobian() serves, and fused_ok() without
+	// Sine behind a lone grid of 2 or 3 input dimensions, 2, 4 or 8 features per level and at most 64 encoded columns,
+	// with neither max_level nor stochastic interpolation in effect. Else it says which of these the module misses.
+	std::string jvp_refusal() const;
+	void jvp(hipStream_t st, uint32_t B, const float* x, const float* directions, uint32_t n_directions, const float* params, float* y,
+	         float* Jv, F32Layouts lay = {});
 	const float* aos_positions(hipStream_t st, uint32_t B, const float* pos_soa);
 	DevBuf pos_aos, dy_aos, dx_aos;  // grow-only scratch of SoA calls
 	// Second order with respect to the input, from a forward's keep: dL_ddLdinput = dL2/d(dL/dinput) fp32

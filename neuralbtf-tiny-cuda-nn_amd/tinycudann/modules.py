@@ -237,6 +237,23 @@ class _NativeModule:
                                                        3 if soa else 0))
         return out, jac
 
+    def jvp(self, input, directions, params, n_out, soa):
+        """tcnn_module_inference_jvp: input [B, D], directions [B, K, D] or None (the unit vectors, K = D) ->
+        (output [B, padded n_out], Jv [B, n_out, K]); soa: input [D, B], directions [K, D, B] -> (output [n_out, B],
+        Jv [n_out, K, B])"""
+        assert input.dtype == torch.float32 and input.is_contiguous() and input.shape[0 if soa else 1] == self._n_in
+        assert params.dtype == self._param_dtype and params.numel() == self._n_params
+        B, D, dev = input.shape[1 if soa else 0], self._n_in, input.device
+        K = D if directions is None else directions.shape[0 if soa else 1]
+        if directions is not None:
+            assert directions.dtype == torch.float32 and directions.is_contiguous()
+            assert tuple(directions.shape) == ((K, D, B) if soa else (B, K, D))
+        out = torch.empty((n_out, B) if soa else (B, self._n_out), dtype=self._out_dtype, device=dev)
+        jv = torch.empty((n_out, K, B) if soa else (B, n_out, K), dtype=torch.float32, device=dev)
+        L.check(L.lib().tcnn_module_inference_jvp(self.h, _stream(input), B, _ptr(input), _ptr(directions), 0 if directions is None else K,
+                                                  _ptr(out), _ptr(jv), _ptr(params), 3 if soa else 0))
+        return out, jv
+
     def bwd_bwd_input(self, ctx, input, params, dL_ddLdinput, dL_doutput):
         """bindings.cpp:185-239: second-order gradients from dL/d(dL/dinput)."""
         B = input.shape[0]
@@ -431,7 +448,31 @@ class Module(torch.nn.Module):
         with J[b, o, d] = dy_o / dx_d and y the bits forward(x) returns. Inference only: no autograd graph is recorded,
         the results do not require grad and gradients do not flow through this call to x or to the parameters (use
         forward and autograd.grad for that). Served by fp32 FullyFusedMLP modules (dtype=torch.float32): a Network, or
-        a NetworkWithInputEncoding behind a lone Identity encoding; every activation but Sine."""
+        a NetworkWithInputEncoding behind a lone Identity encoding or behind a lone grid encoding (the latter through
+        tcnn_module_inference_jvp with the unit directions); every activation but Sine."""
+        return self._value_and_jvp(x, None, layout, unit_call=self._grid_in_front())
+
+    def value_and_jvp(self, x, v, layout="aos"):
+        """f(x) and directional input derivatives (Jacobian-vector products) at inference, in one forward-mode launch
+        that keeps nothing (tcnn_module_inference_jvp):
+        layout="aos": x [B, n_input_dims], v [B, n_input_dims] -> (y [B, n_output_dims], Jv [B, n_output_dims]), or
+                      v [B, K, n_input_dims] -> Jv [B, n_output_dims, K];
+        layout="soa": x [n_input_dims, B], v [n_input_dims, B] -> (y [n_output_dims, B], Jv [n_output_dims, B]), or
+                      v [K, n_input_dims, B] -> Jv [n_output_dims, K, B],
+        with Jv[b, o, k] = sum_d dy_o / dx_d v[b, k, d] and y the bits forward(x) returns. Inference only, as
+        value_and_jacobian. Served by the modules value_and_jacobian serves."""
+        if v.dim() not in (2, 3):
+            raise ValueError(f"v must be [B, D] or [B, K, D] ([D, B] or [K, D, B] for layout='soa'), got {tuple(v.shape)}")
+        y, jv = self._value_and_jvp(x, v if v.dim() == 3 else v.unsqueeze(0 if layout == "soa" else 1), layout, unit_call=False)
+        return y, (jv if v.dim() == 3 else jv.squeeze(1 if layout == "soa" else 2))
+
+    def _grid_in_front(self):
+        """a grid encoding stands alone in front of the network"""
+        return self.native_tcnn_module.hyperparams().get("encoding", {}).get("otype") == "Grid"
+
+    def _value_and_jvp(self, x, v, layout, unit_call):
+        """v None: the Jacobian, from tcnn_module_inference_jvp with null directions when unit_call, else from
+        tcnn_module_inference_jacobian"""
         if layout not in ("aos", "soa"):
             raise ValueError(f"layout must be 'aos' or 'soa', got {layout!r}")
         soa = layout == "soa"
@@ -442,11 +483,20 @@ class Module(torch.nn.Module):
             batch_size = x.shape[1 if soa else 0]
             g = _granularity()
             padded = (batch_size + g - 1) // g * g
-            if batch_size != padded:
-                x = torch.nn.functional.pad(x, [0, padded - batch_size] if soa else [0, 0, 0, padded - batch_size])
-            x = x.to(torch.float).contiguous()
+
+            def prepare(t):
+                if batch_size != padded:
+                    t = torch.nn.functional.pad(t, [0, padded - batch_size] if soa else [0, 0] * (t.dim() - 1) + [0, padded - batch_size])
+                return t.to(torch.float).contiguous()
+
+            x = prepare(x)
             params = self.params.detach().to(self.native_tcnn_module._param_dtype).contiguous()
-            y, jac = self.native_tcnn_module.jacobian(x, params, self.n_output_dims, soa)
+            if v is None and not unit_call:
+                y, jac = self.native_tcnn_module.jacobian(x, params, self.n_output_dims, soa)
+            else:
+                if v is not None and v.shape[2 if soa else 0] != batch_size:
+                    raise ValueError(f"v has another batch size than x: {tuple(v.shape)}")
+                y, jac = self.native_tcnn_module.jvp(x, None if v is None else prepare(v.to(x.device)), params, self.n_output_dims, soa)
             if soa:
                 return (y, jac) if batch_size == padded else (y[:, :batch_size], jac[:, :, :batch_size])
             return y[:batch_size, :self.n_output_dims], jac[:batch_size]
