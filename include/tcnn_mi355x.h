@@ -153,6 +153,28 @@ int tcnn_module_inference_jacobian(tcnn_module* m, void* stream, uint32_t n, con
  * has no backward from its forward value. */
 int tcnn_module_inference_jvp(tcnn_module* m, void* stream, uint32_t n, const float* input, const float* directions,
                               uint32_t n_directions, void* output, float* jvp, const void* params, uint32_t layouts);
+/* Training through tcnn_module_inference_jvp (beyond the reference): dL/dparams of a loss L(output, jvp) on the value
+ * and on the directional derivatives, for all outputs and all directions in one reverse pass.
+ * tcnn_module_forward_jvp is tcnn_module_inference_jvp on AoS matrices (layouts 0), the same bits in output and jvp,
+ * and returns a context that holds the value's and every tangent's row of every layer.
+ * tcnn_module_backward_jvp takes dL_doutput, fp32 [n][padded n_output_dims] (columns past the unpadded width count as
+ * zero), and dL_djvp, fp32 [n][n_output_dims][n_directions] like jvp. Either may be NULL, meaning zero; a call with
+ * both NULL fails. dL_dparams, fp32 [n_params] = [mlp | encoding], is overwritten. input, directions and params are
+ * the forward's; a context whose input, directions or params pointer differs runs the forward again. The network's
+ * part of dL_dparams is bit-reproducible; a grid's part is summed by fp32 atomics and is not. dL/dinput and
+ * dL/ddirections are NOT produced.
+ * The two calls take no `layouts` argument: every matrix is AoS, so there is no mask for them to refuse
+ * (batch-contiguous matrices are a follow-up).
+ * Served: the modules tcnn_module_inference_jvp serves, n a multiple of 256, at most 3 directions at widths 16, 32 and
+ * 64 and 1 at width 128 (NULL directions count as n_input_dims). Anything else answers "<name>[ behind <encoding>]:
+ * forward_jvp / backward_jvp are not implemented by the MI355X engine yet (fp32 FullyFusedMLP network modules alone,
+ * behind a lone Identity encoding or behind a lone grid encoding only; AoS matrices, batches of 256, at most 3
+ * directions, 1 at width 128)[: <what is not served>]". */
+tcnn_context* tcnn_module_forward_jvp(tcnn_module* m, void* stream, uint32_t n, const float* input, const float* directions,
+                                      uint32_t n_directions, void* output, float* jvp, const void* params);
+int tcnn_module_backward_jvp(tcnn_module* m, void* stream, const tcnn_context* ctx, uint32_t n, const void* dL_doutput,
+                             const float* dL_djvp, void* dL_dparams, const float* input, const float* directions,
+                             const void* params);
 /* The torch binding's backward with its loss-scale arithmetic folded in (reference
  * bindings/torch/tinycudann/modules.py:128-138): dL_doutput (fp16) is multiplied by loss_scale and
  * rounded to fp16, the module's backward runs on it, dL_dinput (fp32) is divided by loss_scale and

@@ -100,6 +100,15 @@ public:
 	virtual void inference_jvp(hipStream_t, uint32_t, const float*, const float*, uint32_t, void*, float*, const void*, uint32_t = 0) {
 		throw std::runtime_error(name() + ": inference_jvp is not implemented");
 	}
+	// Beyond the reference: inference_jvp keeping a context, and its reverse pass, dL_dparams (fp32, overwritten) of a
+	// loss on the output and on the product (tcnn_module_forward_jvp / tcnn_module_backward_jvp). dL_doutput or dL_djvp
+	// may be null (zero), not both. dL/dinput and dL/ddirections are not produced.
+	virtual Context forward_jvp(hipStream_t, uint32_t, const float*, const float*, uint32_t, void*, float*, const void*) {
+		throw std::runtime_error(name() + ": forward_jvp is not implemented");
+	}
+	virtual void backward_jvp(hipStream_t, const Context&, uint32_t, const void*, const float*, void*, const float*, const float*, const void*) {
+		throw std::runtime_error(name() + ": backward_jvp is not implemented");
+	}
 
 	virtual uint32_t n_input_dims() const = 0;
 	virtual uint32_t n_output_dims() const = 0;
@@ -152,6 +161,15 @@ public:
 	void inference_jvp(hipStream_t stream, uint32_t n, const float* input, const float* directions, uint32_t n_directions, void* output,
 	                   float* jvp, const void* params, uint32_t layouts = 0) override {
 		check(tcnn_module_inference_jvp(m_h, stream, n, input, directions, n_directions, output, jvp, params, layouts));
+	}
+	Context forward_jvp(hipStream_t stream, uint32_t n, const float* input, const float* directions, uint32_t n_directions, void* output,
+	                    float* jvp, const void* params) override {
+		tcnn_context* c = check_ptr(tcnn_module_forward_jvp(m_h, stream, n, input, directions, n_directions, output, jvp, params));
+		return Context{std::make_unique<NativeContext>(c)};
+	}
+	void backward_jvp(hipStream_t stream, const Context& ctx, uint32_t n, const void* dL_doutput, const float* dL_djvp, void* dL_dparams,
+	                  const float* input, const float* directions, const void* params) override {
+		check(tcnn_module_backward_jvp(m_h, stream, native(ctx), n, dL_doutput, dL_djvp, dL_dparams, input, directions, params));
 	}
 	uint32_t n_input_dims() const override { return tcnn_module_n_input_dims(m_h); }
 	uint32_t n_output_dims() const override { return tcnn_module_n_output_dims(m_h); }

@@ -139,6 +139,21 @@ struct ModuleBase {
 		                         "behind a lone Identity encoding or behind a lone grid encoding only)" + (why.empty() ? "" : ": " + why));
 	}
 	virtual void inference_jvp(hipStream_t, uint32_t, const float*, const float*, uint32_t, void*, float*, const void*, uint32_t) { refuse_jvp(); }
+	// Training through value and Jacobian-vector products (tcnn_module_forward_jvp / tcnn_module_backward_jvp): what
+	// inference_jvp serves, on AoS matrices, in batches of 256, with at most 3 directions (1 at width 128)
+	void refuse_jvp_train(const std::string& front = "", const std::string& why = "") const {
+		throw std::runtime_error(name() + (front.empty() ? "" : " behind " + front) +
+		                         ": forward_jvp / backward_jvp are not implemented by the MI355X engine yet (fp32 FullyFusedMLP network modules "
+		                         "alone, behind a lone Identity encoding or behind a lone grid encoding only; AoS matrices, batches of 256, at "
+		                         "most 3 directions, 1 at width 128)" + (why.empty() ? "" : ": " + why));
+	}
+	virtual std::unique_ptr<ModuleCtx> forward_jvp(hipStream_t, uint32_t, const float*, const float*, uint32_t, void*, float*, const void*) {
+		refuse_jvp_train();
+		return nullptr;
+	}
+	virtual void backward_jvp(hipStream_t, const ModuleCtx*, uint32_t, const void*, const float*, void*, const float*, const float*, const void*) {
+		refuse_jvp_train();
+	}
 	virtual GridEncodingHost* grid_encoding() { return nullptr; }
 	// precision of the parameters, the output, dL/doutput and dL/dparams (TCNN_PRECISION_*): fp16 for
 	// every module but an encoding or a network created with Fp32
@@ -372,6 +387,70 @@ struct ModuleNWIEF32 : ModuleBase {
 		if (!n) return;
 		TCNN_CHECK(in && out && jvp && params, "inference_jvp needs the input, the output, the product and the parameters");
 		model.jvp(st, n, in, directions, n_directions, (const float*)params, (float*)out, jvp, F32Layouts(mask));
+	}
+	// The same call keeping a context, and its reverse pass: dL/dparams of a loss on the output and on the product
+	// (beyond the reference). AoS matrices only; null directions are the unit vectors and count as n_input_dims.
+	struct JvpCtx : ModuleCtx {
+		std::shared_ptr<KeepPool> pool;
+		std::unique_ptr<DevBuf> keep;
+		const float* in = nullptr;
+		const float* directions = nullptr;
+		const void* params = nullptr;
+		uint32_t K = 0;
+		~JvpCtx() override {
+			if (pool && keep) pool->put(std::move(keep));
+		}
+	};
+	uint32_t check_jvp_train(uint32_t n, const float* directions, uint32_t n_directions) const {
+		if (!model.fused_ok()) refuse_jvp_train();
+		const EncodingHost::Part* lone = model.enc->lone_part();
+		if (!lone || (lone->kind != COMP_IDENTITY && lone->kind != COMP_GRID)) refuse_jvp_train(model.enc->name());
+		TCNN_CHECK(directions ? n_directions >= 1 : (n_directions == 0 || n_directions == model.n_input_dims),
+		           "forward_jvp: n_directions must be at least 1, or 0 or the input width with null directions (the unit vectors)");
+		const uint32_t K = directions ? n_directions : model.n_input_dims;
+		const std::string why = model.jvp_train_refusal(n, K);
+		if (!why.empty()) refuse_jvp_train(model.enc->name(), why);
+		return K;
+	}
+	std::unique_ptr<ModuleCtx> forward_jvp(hipStream_t st, uint32_t n, const float* in, const float* directions, uint32_t n_directions, void* out,
+	                                       float* jvp, const void* params) override {
+		const uint32_t K = check_jvp_train(n, directions, n_directions);  // names the module and the reason, the batch among them
+		check_batch(n);
+		auto c = std::make_unique<JvpCtx>();
+		c->K = K;
+		if (!n) return c;
+		TCNN_CHECK(in && out && jvp && params, "forward_jvp needs the input, the output, the product and the parameters");
+		c->pool = pool;
+		c->keep = pool->get();
+		c->keep->reserve(model.jvp_keep_floats(n, K) * 4);
+		model.jvp_forward(st, n, in, directions, K, (const float*)params, (float*)out, jvp, c->keep->as<float>());
+		c->in = in;
+		c->directions = directions;
+		c->params = params;
+		return c;
+	}
+	// the keep rule is the backward's: a context whose input, directions or parameters differ recomputes the forward
+	void backward_jvp(hipStream_t st, const ModuleCtx* ctx, uint32_t n, const void* dL_dout, const float* dL_djvp, void* dL_dparams,
+	                  const float* in, const float* directions, const void* params) override {
+		const JvpCtx* c = dynamic_cast<const JvpCtx*>(ctx);
+		TCNN_CHECK(c, "backward_jvp: the context does not come from forward_jvp");
+		TCNN_CHECK(dL_dout || dL_djvp, "backward_jvp: dL_doutput and dL_djvp are both null: there is nothing to differentiate");
+		if (!directions && c->K != model.n_input_dims)
+			refuse_jvp_train(model.enc->name(), "the forward ran " + std::to_string(c->K) + " directions and the backward was given none (null directions "
+			                                    "are the " + std::to_string(model.n_input_dims) + " unit vectors): pass the forward's directions");
+		check_jvp_train(n, directions, directions ? c->K : 0);
+		check_batch(n);
+		if (!n || !dL_dparams) return;
+		TCNN_CHECK(in && params, "backward_jvp needs the input and the parameters");
+		const float* keep = c->keep ? c->keep->as<float>() : nullptr;
+		if (!keep || c->in != in || c->directions != directions || c->params != params) {
+			const size_t nk = model.jvp_keep_floats(n, c->K);
+			rekeep.reserve((nk + (size_t)n * model.mlp.padded_output + (size_t)n * model.n_output_dims * c->K) * 4);
+			float* y = rekeep.as<float>() + nk;
+			model.jvp_forward(st, n, in, directions, c->K, (const float*)params, y, y + (size_t)n * model.mlp.padded_output, rekeep.as<float>());
+			keep = rekeep.as<float>();
+		}
+		model.jvp_backward(st, n, in, directions, c->K, (const float*)params, (const float*)dL_dout, dL_djvp, keep, (float*)dL_dparams);
 	}
 	GridEncodingHost* grid_encoding() override { return model.enc->lone_grid(); }
 	// "fused" / "chain": the whole network in one launch (mlp_f32_fused.hip); the weight gradients stay per layer
@@ -637,6 +716,29 @@ int tcnn_module_inference_jvp(tcnn_module* m, void* stream, uint32_t n, const fl
 		TCNN_CHECK(m && m->m, "inference_jvp: null module");
 		// an empty batch still answers for the module: a refusal does not depend on n
 		m->m->inference_jvp((hipStream_t)stream, n, in, directions, n_directions, out, jvp, params, layouts);
+	});
+}
+
+tcnn_context* tcnn_module_forward_jvp(tcnn_module* m, void* stream, uint32_t n, const float* in, const float* directions, uint32_t n_directions,
+                                      void* out, float* jvp, const void* params) {
+	return guard_ptr<tcnn_context>([&] {
+		TCNN_CHECK(m && m->m, "forward_jvp: null module");
+		auto c = std::make_unique<tcnn_context>();
+		c->n = n;
+		// an empty batch still answers for the module: a refusal does not depend on n
+		c->impl = m->m->forward_jvp((hipStream_t)stream, n, in, directions, n_directions, out, jvp, params);
+		return c.release();
+	});
+}
+
+int tcnn_module_backward_jvp(tcnn_module* m, void* stream, const tcnn_context* ctx, uint32_t n, const void* dL_dout, const float* dL_djvp,
+                             void* dL_dparams, const float* in, const float* directions, const void* params) {
+	return guard([&] {
+		TCNN_CHECK(m && m->m, "backward_jvp: null module");
+		TCNN_CHECK(ctx != nullptr, "backward_jvp: null context");
+		TCNN_CHECK(ctx->n == n, "backward_jvp: batch size differs from the forward's");
+		m->m->backward_jvp((hipStream_t)stream, ctx->impl.get(), n, dL_dout, dL_djvp, dL_dparams, in, directions, params);
+		if (n == 0 && dL_dparams) TCNN_HIP_CHECK(hipMemsetAsync(dL_dparams, 0, m->m->n_params() * m->m->elem_bytes(), (hipStream_t)stream));
 	});
 }
 

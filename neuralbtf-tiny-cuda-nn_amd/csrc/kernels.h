@@ -510,6 +510,30 @@ bool f32_mlp_jvp_grid_ok(uint32_t D, uint32_t F, uint32_t IN);
 void launch_f32_mlp_jvp(hipStream_t st, uint32_t B, uint32_t D, uint32_t IN, uint32_t W, uint32_t NH, uint32_t OUTP, uint32_t n_out,
                         const float* params, const float* x, const float* directions, uint32_t n_directions, bool x_soa, float* y, float* jvp,
                         bool y_soa, int act, int out_act, const GridCall* grid, const float* table, float scale, float offset);
+// Training through that call (mlp_f32_jvp_train.hip): dL/dparams of a loss L(y, Jv). AoS only, B a multiple of 256,
+// K = n_directions <= f32_mlp_jvp_train_max_directions(W) (3 up to W 64, 1 at W 128), so the forward is one pass.
+uint32_t f32_mlp_jvp_train_max_directions(uint32_t W);
+// The context of the keeping forward, nq = 1 + K: X_0 [nq][B][IN] | X_1 .. X_NH [nq][B][W] | y [B][OUTP] | S_0 ..
+// S_{NH-1} [K][B][W] | S_NH [K][B][OUTP]; X_j = (h_j, t_{j,1..K}) is the input side of layer j, S_j the tangents before
+// the gate (written only for an activation with curvature). The reverse chain's stack: G_0 .. G_{NH-1} [nq][B][W] |
+// G_NH [nq][B][OUTP] | (hb_0, tb_{0,1..K}) [nq][B][IN], G_j = (zb_j, sb_{j,1..K}).
+size_t f32_mlp_jvp_keep_floats(uint32_t B, uint32_t K, uint32_t IN, uint32_t W, uint32_t NH, uint32_t OUTP);
+size_t f32_mlp_jvp_stack_floats(uint32_t B, uint32_t K, uint32_t IN, uint32_t W, uint32_t NH, uint32_t OUTP);
+size_t f32_mlp_jvp_keep_x(uint32_t B, uint32_t K, uint32_t IN, uint32_t W, uint32_t NH, uint32_t OUTP, uint32_t j);   // X_j, j <= NH
+size_t f32_mlp_jvp_stack_g(uint32_t B, uint32_t K, uint32_t IN, uint32_t W, uint32_t NH, uint32_t OUTP, uint32_t j);  // G_j; j = NH + 1: hb_0
+// launch_f32_mlp_jvp on AoS matrices, with the same bits in y and jvp, writing the context
+void launch_f32_mlp_jvp_keep(hipStream_t st, uint32_t B, uint32_t D, uint32_t IN, uint32_t W, uint32_t NH, uint32_t OUTP, uint32_t n_out,
+                             const float* params, const float* x, const float* directions, uint32_t n_directions, float* y, float* jvp,
+                             int act, int out_act, const GridCall* grid, const float* table, float scale, float offset, float* keep);
+// from dL_dy [B][OUTP] and dL_djvp [B][n_out][K] (either nullable: zero) down to the encoded row, filling the stack;
+// want_d0: also (hb_0, tb_0), which only an encoding with parameters reads
+void launch_f32_mlp_jvp_bwd_chain(hipStream_t st, uint32_t B, uint32_t IN, uint32_t W, uint32_t NH, uint32_t OUTP, uint32_t n_out, uint32_t K,
+                                  const float* params, const float* keep, const float* dL_dy, const float* dL_djvp, float* stack, bool want_d0,
+                                  int act, int out_act);
+// grad[idx_c][f] += sum_d (dw_c / dx_d) sum_k v_k[d] t0[k][b][l F + f] by fp32 atomics: the tangent term of the table
+// gradient. directions [B][K][D], null: the unit vectors (K = D); t0 [K][B][IN]. Nearest: nothing to add.
+void launch_grid_jvp_bwd_f32(hipStream_t st, const GridCall& g, uint32_t B, uint32_t K, uint32_t IN, const float* x, const float* directions,
+                             const float* t0, float* grad);
 // dst[C][R] = src[R][C]^T
 void launch_f32_transpose(hipStream_t st, uint32_t R, uint32_t C, const float* src, float* dst);
 

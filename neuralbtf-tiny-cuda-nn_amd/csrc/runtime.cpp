@@ -1346,6 +1346,67 @@ void NetworkF32Host::jvp(hipStream_t st, uint32_t B, const float* x, const float
 	                   p->grid ? params + mlp.n_params() + p->param_offset : nullptr, p->f0, p->f1);
 }
 
+std::string NetworkF32Host::jvp_train_refusal(uint32_t B, uint32_t K) const {
+	const std::string why = jvp_refusal();
+	if (!why.empty()) return why;
+	const uint32_t max_k = f32_mlp_jvp_train_max_directions(mlp.width);
+	if (K < 1 || K > max_k)
+		return std::to_string(K) + " directions at width " + std::to_string(mlp.width) + " (at most " + std::to_string(max_k) +
+		       " are served; the unit vectors count as the input width)";
+	if (B % 256 != 0) return "a batch of " + std::to_string(B) + " (a multiple of 256 is served)";
+	return "";
+}
+
+size_t NetworkF32Host::jvp_keep_floats(uint32_t B, uint32_t K) const {
+	return f32_mlp_jvp_keep_floats(B, K, mlp.n_input, mlp.width, mlp.n_hidden_layers, mlp.padded_output);
+}
+
+void NetworkF32Host::jvp_forward(hipStream_t st, uint32_t B, const float* x, const float* directions, uint32_t K, const float* params, float* y,
+                                 float* Jv, float* keep) {
+	const std::string why = jvp_train_refusal(B, K);
+	TCNN_CHECK(why.empty(), "fp32 network: no training through the Jacobian-vector product: " + why);
+	const EncodingHost::Part* p = enc->lone_part();
+	const GridCall gc = p->grid ? p->grid->call() : GridCall{};
+	launch_f32_mlp_jvp_keep(st, B, n_input_dims, mlp.n_input, mlp.width, mlp.n_hidden_layers, mlp.padded_output, n_output_dims, params, x,
+	                        directions, K, y, Jv, mlp.activation, mlp.output_activation, p->grid ? &gc : nullptr,
+	                        p->grid ? params + mlp.n_params() + p->param_offset : nullptr, p->f0, p->f1, keep);
+}
+
+void NetworkF32Host::jvp_backward(hipStream_t st, uint32_t B, const float* x, const float* directions, uint32_t K, const float* params,
+                                  const float* dL_dy, const float* dL_dJv, const float* keep, float* dL_dparams) {
+	const std::string why = jvp_train_refusal(B, K);
+	TCNN_CHECK(why.empty(), "fp32 network: no training through the Jacobian-vector product: " + why);
+	if (!B || !dL_dparams) return;
+	const uint32_t W = mlp.width, IN = mlp.n_input, NH = mlp.n_hidden_layers, OUTP = mlp.padded_output;
+	const uint32_t n_mlp = mlp.n_params(), n_enc = enc->n_params();
+	const GridEncodingHost* grid = enc->lone_grid();
+	jvp_stack.reserve(f32_mlp_jvp_stack_floats(B, K, IN, W, NH, OUTP) * 4);
+	float* stack = jvp_stack.as<float>();
+	launch_f32_mlp_jvp_bwd_chain(st, B, IN, W, NH, OUTP, n_output_dims, K, params, keep, dL_dy, dL_dJv, stack, grid != nullptr, mlp.activation,
+	                             mlp.output_activation);
+	// dW_j = G_j^T X_j over the (1 + K) B stacked rows: the gate is already applied, so the product takes no activation
+	const uint32_t rows = (1 + K) * B, nsl = f32_wgrad_n_slabs(rows);
+	wgrad_partial.reserve((size_t)nsl * std::max(W, OUTP) * std::max(W, IN) * 4);
+	for (uint32_t j = 0; j <= NH; ++j) {
+		const uint32_t N = j < NH ? W : OUTP, Kj = j == 0 ? IN : W;
+		const size_t off = j == 0 ? 0 : (size_t)W * IN + (size_t)(j - 1) * W * W;
+		launch_f32_wgrad(st, rows, N, Kj, stack + f32_mlp_jvp_stack_g(B, K, IN, W, NH, OUTP, j), nullptr, ACT_NONE,
+		                 keep + f32_mlp_jvp_keep_x(B, K, IN, W, NH, OUTP, j), wgrad_partial.as<float>());
+		const size_t tf = reduce_partials_tmp_floats(nsl, N * Kj);
+		if (tf) red_tmp.reserve(tf * 4);
+		launch_reduce_partials(st, wgrad_partial.as<float>(), nsl, N * Kj, N * Kj, dL_dparams + off, red_tmp.as<float>());
+	}
+	if (!grid) return;
+	// the table: w_c hb_0 through the first-order backward, then the tangent term by atomics onto zeros, added
+	const float* hb0 = stack + f32_mlp_jvp_stack_g(B, K, IN, W, NH, OUTP, NH + 1);
+	enc->backward_params(st, B, x, hb0, 2, dL_dparams + n_mlp);
+	if (grid->desc.interp == Interp::Nearest) return;
+	grid_tmp.reserve((size_t)n_enc * 4);
+	TCNN_HIP_CHECK(hipMemsetAsync(grid_tmp.p, 0, (size_t)n_enc * 4, st));
+	launch_grid_jvp_bwd_f32(st, grid->call(), B, K, IN, x, directions, hb0 + (size_t)B * IN, grid_tmp.as<float>());
+	launch_f32_add(st, n_enc, dL_dparams + n_mlp, grid_tmp.as<float>());
+}
+
 const float* NetworkF32Host::aos_positions(hipStream_t st, uint32_t B, const float* pos_soa) {
 	pos_aos.reserve((size_t)B * n_input_dims * 4);
 	launch_f32_transpose(st, n_input_dims, B, pos_soa, pos_aos.as<float>());

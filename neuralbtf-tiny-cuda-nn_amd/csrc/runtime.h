@@ -561,6 +561,20 @@ struct NetworkF32Host {
 	std::string jvp_refusal() const;
 	void jvp(hipStream_t st, uint32_t B, const float* x, const float* directions, uint32_t n_directions, const float* params, float* y,
 	         float* Jv, F32Layouts lay = {});
+	// Training through jvp() (mlp_f32_jvp_train.hip): dL/dparams of a loss L(y, Jv). jvp_forward is jvp() on AoS
+	// matrices, the same bits in y and Jv, and fills keep (jvp_keep_floats(B, K) floats; K counts the unit vectors as
+	// n_input_dims). jvp_backward takes dL_dy [B][padded_output] and dL_dJv [B][n_output_dims][K] (either null: zero, not
+	// both) and overwrites dL_dparams [n_params()]: one reverse-chain launch, one weight-gradient product per layer over
+	// the (1 + K) B stacked rows, and for a grid the value term through its first-order backward plus the tangent term by
+	// fp32 atomics. The network's part is bit-reproducible, the grid's is not. dL/dx and dL/dv are not produced.
+	// Served when jvp_train_refusal(B, K) is empty: what jvp_refusal() accepts, B a multiple of 256, K <= 3 (1 at W 128).
+	std::string jvp_train_refusal(uint32_t B, uint32_t K) const;
+	size_t jvp_keep_floats(uint32_t B, uint32_t K) const;
+	void jvp_forward(hipStream_t st, uint32_t B, const float* x, const float* directions, uint32_t K, const float* params, float* y, float* Jv,
+	                 float* keep);
+	void jvp_backward(hipStream_t st, uint32_t B, const float* x, const float* directions, uint32_t K, const float* params, const float* dL_dy,
+	                  const float* dL_dJv, const float* keep, float* dL_dparams);
+	DevBuf jvp_stack;  // grow-only scratch of jvp_backward: the reverse chain's adjoints
 	const float* aos_positions(hipStream_t st, uint32_t B, const float* pos_soa);
 	DevBuf pos_aos, dy_aos, dx_aos;  // grow-only scratch of SoA calls
 	// Second order with respect to the input, from a forward's keep: dL_ddLdinput = dL2/d(dL/dinput) fp32

@@ -254,6 +254,24 @@ class _NativeModule:
                                                   _ptr(out), _ptr(jv), _ptr(params), 3 if soa else 0))
         return out, jv
 
+    def fwd_jvp(self, input, directions, params, n_out):
+        """tcnn_module_forward_jvp: jvp() on AoS matrices, keeping a context for bwd_jvp"""
+        B, D = input.shape[0], self._n_in
+        K = D if directions is None else directions.shape[1]
+        out = torch.empty(B, self._n_out, dtype=self._out_dtype, device=input.device)
+        jv = torch.empty(B, n_out, K, dtype=torch.float32, device=input.device)
+        ctx = L.check_ptr(L.lib().tcnn_module_forward_jvp(self.h, _stream(input), B, _ptr(input), _ptr(directions),
+                                                           0 if directions is None else K, _ptr(out), _ptr(jv), _ptr(params)))
+        return _NativeContext(ctx), out, jv
+
+    def bwd_jvp(self, ctx, input, directions, params, dL_doutput, dL_djvp):
+        """tcnn_module_backward_jvp: dL_doutput [B, padded n_out] and dL_djvp [B, n_out, K] (either None: zero) ->
+        dL_dparams"""
+        dL_dparams = torch.empty(self._n_params, dtype=self._param_dtype, device=input.device)
+        L.check(L.lib().tcnn_module_backward_jvp(self.h, _stream(input), ctx.h, input.shape[0], _ptr(dL_doutput), _ptr(dL_djvp),
+                                                 _ptr(dL_dparams), _ptr(input), _ptr(directions), _ptr(params)))
+        return dL_dparams
+
     def bwd_bwd_input(self, ctx, input, params, dL_ddLdinput, dL_doutput):
         """bindings.cpp:185-239: second-order gradients from dL/d(dL/dinput)."""
         B = input.shape[0]
@@ -382,6 +400,34 @@ class _module_function_soa(torch.autograd.Function):
         return None, input_grad, params_grad, None, None
 
 
+class _jvp_function(torch.autograd.Function):
+    """value_and_jvp / value_and_jacobian with differentiable=True: the output and the product carry a graph to the
+    parameters (tcnn_module_forward_jvp / tcnn_module_backward_jvp). First order, parameters only."""
+
+    @staticmethod
+    def forward(ctx, native_tcnn_module, input, directions, params, n_out):
+        ctx.set_materialize_grads(False)
+        native_ctx, output, jv = native_tcnn_module.fwd_jvp(input, directions, params, n_out)
+        ctx.save_for_backward(input, params)
+        ctx.directions = directions
+        ctx.native_tcnn_module = native_tcnn_module
+        ctx.native_ctx = native_ctx
+        return output, jv
+
+    @staticmethod
+    def backward(ctx, doutput, djv):
+        if torch.is_grad_enabled():
+            raise ValueError("value_and_jvp(differentiable=True) is differentiable once: a double backward through it "
+                             "(create_graph=True) is not implemented")
+        if doutput is None and djv is None:
+            return None, None, None, None, None
+        input, params = ctx.saved_tensors
+        doutput = None if doutput is None else doutput.to(torch.float32).contiguous()
+        djv = None if djv is None else djv.to(torch.float32).contiguous()
+        params_grad = ctx.native_tcnn_module.bwd_jvp(ctx.native_ctx, input, ctx.directions, params, doutput, djv)
+        return None, None, None, params_grad, None
+
+
 class Module(torch.nn.Module):
     def __init__(self, seed=1337):
         super().__init__()
@@ -441,7 +487,7 @@ class Module(torch.nn.Module):
         output = _module_function_soa.apply(self.native_tcnn_module, x, params, self.loss_scale, self.n_output_dims)
         return output if batch_size == padded else output[:, :batch_size]
 
-    def value_and_jacobian(self, x, layout="aos"):
+    def value_and_jacobian(self, x, layout="aos", differentiable=False):
         """f(x) and its input Jacobian at inference, in one forward-mode launch that keeps nothing:
         layout="aos": x [B, n_input_dims] -> (y [B, n_output_dims], J [B, n_output_dims, n_input_dims]);
         layout="soa": x [n_input_dims, B] -> (y [n_output_dims, B], J [n_output_dims, n_input_dims, B]),
@@ -449,10 +495,38 @@ class Module(torch.nn.Module):
         the results do not require grad and gradients do not flow through this call to x or to the parameters (use
         forward and autograd.grad for that). Served by fp32 FullyFusedMLP modules (dtype=torch.float32): a Network, or
         a NetworkWithInputEncoding behind a lone Identity encoding or behind a lone grid encoding (the latter through
-        tcnn_module_inference_jvp with the unit directions); every activation but Sine."""
+        tcnn_module_inference_jvp with the unit directions); every activation but Sine.
+        differentiable=True: as value_and_jvp."""
+        if differentiable:
+            return self._value_and_jvp_differentiable(x, None, layout)
         return self._value_and_jvp(x, None, layout, unit_call=self._grid_in_front())
 
-    def value_and_jvp(self, x, v, layout="aos"):
+    def _value_and_jvp_differentiable(self, x, v, layout):
+        """v [B, K, D] or None (the unit vectors): (y, Jv [B, n_output_dims, K]) with a graph to the parameters"""
+        if layout != "aos":
+            raise ValueError(f"differentiable=True serves layout='aos' only (batch-contiguous matrices are not implemented), got {layout!r}")
+        if x.requires_grad or (v is not None and v.requires_grad):
+            raise ValueError("differentiable=True produces the gradient of the parameters only: dL/dx and dL/dv are not implemented, "
+                             "so x and v must not require grad (detach them, or use forward and autograd.grad)")
+        if not x.is_cuda:
+            warnings.warn("input must be a CUDA tensor, but isn't. This indicates suboptimal performance.")
+            x = x.cuda()
+        batch_size = x.shape[0]
+        if v is not None and v.shape[0] != batch_size:
+            raise ValueError(f"v has another batch size than x: {tuple(v.shape)}")
+        padded = (batch_size + 255) // 256 * 256  # the reverse pass runs whole 256-row granules
+
+        def prepare(t):
+            if batch_size != padded:
+                t = torch.nn.functional.pad(t, [0, 0] * (t.dim() - 1) + [0, padded - batch_size])
+            return t.to(torch.float).contiguous()
+
+        params = self.params.to(self.native_tcnn_module._param_dtype).contiguous()
+        y, jv = _jvp_function.apply(self.native_tcnn_module, prepare(x), None if v is None else prepare(v.to(x.device)), params,
+                                    self.n_output_dims)
+        return y[:batch_size, :self.n_output_dims], jv[:batch_size]
+
+    def value_and_jvp(self, x, v, layout="aos", differentiable=False):
         """f(x) and directional input derivatives (Jacobian-vector products) at inference, in one forward-mode launch
         that keeps nothing (tcnn_module_inference_jvp):
         layout="aos": x [B, n_input_dims], v [B, n_input_dims] -> (y [B, n_output_dims], Jv [B, n_output_dims]), or
@@ -460,9 +534,17 @@ class Module(torch.nn.Module):
         layout="soa": x [n_input_dims, B], v [n_input_dims, B] -> (y [n_output_dims, B], Jv [n_output_dims, B]), or
                       v [K, n_input_dims, B] -> Jv [n_output_dims, K, B],
         with Jv[b, o, k] = sum_d dy_o / dx_d v[b, k, d] and y the bits forward(x) returns. Inference only, as
-        value_and_jacobian. Served by the modules value_and_jacobian serves."""
+        value_and_jacobian. Served by the modules value_and_jacobian serves.
+        differentiable=True (opt-in; the default is the call above, bit for bit): y and Jv carry the same bits and an
+        autograd graph to the parameters, so a loss on the value and on the derivative trains the module in one keeping
+        forward and one reverse pass (tcnn_module_forward_jvp / tcnn_module_backward_jvp). layout="aos" only, at most 3
+        directions (1 at width 128; the Jacobian counts as n_input_dims), gradients for the parameters only: x or v
+        requiring grad, layout="soa" and a double backward each raise a ValueError."""
         if v.dim() not in (2, 3):
             raise ValueError(f"v must be [B, D] or [B, K, D] ([D, B] or [K, D, B] for layout='soa'), got {tuple(v.shape)}")
+        if differentiable:
+            y, jv = self._value_and_jvp_differentiable(x, v if v.dim() == 3 else v.unsqueeze(1), layout)
+            return y, (jv if v.dim() == 3 else jv.squeeze(2))
         y, jv = self._value_and_jvp(x, v if v.dim() == 3 else v.unsqueeze(0 if layout == "soa" else 1), layout, unit_call=False)
         return y, (jv if v.dim() == 3 else jv.squeeze(1 if layout == "soa" else 2))
 
