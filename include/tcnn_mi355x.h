@@ -153,6 +153,24 @@ int tcnn_module_inference_jacobian(tcnn_module* m, void* stream, uint32_t n, con
  * has no backward from its forward value. */
 int tcnn_module_inference_jvp(tcnn_module* m, void* stream, uint32_t n, const float* input, const float* directions,
                               uint32_t n_directions, void* output, float* jvp, const void* params, uint32_t layouts);
+/* tcnn_module_inference_jvp with the summed second directional derivatives in the same launch, the "forward Laplacian"
+ * (beyond the reference): output and jvp as tcnn_module_inference_jvp writes them, to the bit, and
+ * second[b][o] = sum_k directions[b][k]^T (d^2 output_o / d input^2) directions[b][k], fp32 [n][n_output_dims].
+ * directions == NULL means the n_input_dims unit vectors: jvp is then the Jacobian and second the Laplacian
+ * sum_d d^2 output_o / d input_d^2; one direction gives the curvature v^T H v along it. Nothing is kept.
+ * `layouts` as tcnn_module_inference_jvp; under TCNN_LAYOUT_SOA_OUTPUT second is [n_output_dims][n]. Each result is the
+ * AoS call's to the bit, transposed, and second is bit-reproducible. n: a multiple of 128.
+ * The second derivative of an activation is taken from its forward value like the first: it is zero for None, ReLU and
+ * LeakyReLU, so second is then the grid's own curvature carried through the network (exactly zero behind an Identity,
+ * behind Nearest interpolation, and for the Laplacian behind Linear interpolation).
+ * Served by the modules tcnn_module_inference_jvp serves at widths 16, 32 and 64. Any other module answers
+ * "<name>[ behind <encoding>]: inference_jvp_second is not implemented by the MI355X engine yet (fp32 FullyFusedMLP
+ * network modules alone, behind a lone Identity encoding or behind a lone grid encoding only)[: <what about the grid is
+ * not served>]"; width 128 answers it with ": a width of 128 (16, 32 and 64 are served)", and Sine answers that it has
+ * no backward from its forward value. */
+int tcnn_module_inference_jvp_second(tcnn_module* m, void* stream, uint32_t n, const float* input, const float* directions,
+                                     uint32_t n_directions, void* output, float* jvp, float* second, const void* params,
+                                     uint32_t layouts);
 /* Training through tcnn_module_inference_jvp (beyond the reference): dL/dparams of a loss L(output, jvp) on the value
  * and on the directional derivatives, for all outputs and all directions in one reverse pass.
  * tcnn_module_forward_jvp is tcnn_module_inference_jvp on AoS matrices (layouts 0), the same bits in output and jvp,

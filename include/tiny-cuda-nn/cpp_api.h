@@ -100,6 +100,13 @@ public:
 	virtual void inference_jvp(hipStream_t, uint32_t, const float*, const float*, uint32_t, void*, float*, const void*, uint32_t = 0) {
 		throw std::runtime_error(name() + ": inference_jvp is not implemented");
 	}
+	// Beyond the reference: inference_jvp and second[b][o] = sum_k directions[b][k]^T (d^2 output_o / d input^2)
+	// directions[b][k] in the same launch (tcnn_module_inference_jvp_second); null directions give the Jacobian and the
+	// Laplacian. What inference_jvp serves; any other module throws.
+	virtual void inference_jvp_second(hipStream_t, uint32_t, const float*, const float*, uint32_t, void*, float*, float*, const void*,
+	                                  uint32_t = 0) {
+		throw std::runtime_error(name() + ": inference_jvp_second is not implemented");
+	}
 	// Beyond the reference: inference_jvp keeping a context, and its reverse pass, dL_dparams (fp32, overwritten) of a
 	// loss on the output and on the product (tcnn_module_forward_jvp / tcnn_module_backward_jvp). dL_doutput or dL_djvp
 	// may be null (zero), not both. dL/dinput and dL/ddirections are not produced.
@@ -161,6 +168,10 @@ public:
 	void inference_jvp(hipStream_t stream, uint32_t n, const float* input, const float* directions, uint32_t n_directions, void* output,
 	                   float* jvp, const void* params, uint32_t layouts = 0) override {
 		check(tcnn_module_inference_jvp(m_h, stream, n, input, directions, n_directions, output, jvp, params, layouts));
+	}
+	void inference_jvp_second(hipStream_t stream, uint32_t n, const float* input, const float* directions, uint32_t n_directions,
+	                          void* output, float* jvp, float* second, const void* params, uint32_t layouts = 0) override {
+		check(tcnn_module_inference_jvp_second(m_h, stream, n, input, directions, n_directions, output, jvp, second, params, layouts));
 	}
 	Context forward_jvp(hipStream_t stream, uint32_t n, const float* input, const float* directions, uint32_t n_directions, void* output,
 	                    float* jvp, const void* params) override {

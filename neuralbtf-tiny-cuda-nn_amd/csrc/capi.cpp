@@ -139,6 +139,15 @@ struct ModuleBase {
 		                         "behind a lone Identity encoding or behind a lone grid encoding only)" + (why.empty() ? "" : ": " + why));
 	}
 	virtual void inference_jvp(hipStream_t, uint32_t, const float*, const float*, uint32_t, void*, float*, const void*, uint32_t) { refuse_jvp(); }
+	// That launch with the summed second directional derivatives (tcnn_module_inference_jvp_second): the same modules
+	void refuse_jvp_second(const std::string& front = "", const std::string& why = "") const {
+		throw std::runtime_error(name() + (front.empty() ? "" : " behind " + front) +
+		                         ": inference_jvp_second is not implemented by the MI355X engine yet (fp32 FullyFusedMLP network modules "
+		                         "alone, behind a lone Identity encoding or behind a lone grid encoding only)" + (why.empty() ? "" : ": " + why));
+	}
+	virtual void inference_jvp_second(hipStream_t, uint32_t, const float*, const float*, uint32_t, void*, float*, float*, const void*, uint32_t) {
+		refuse_jvp_second();
+	}
 	// Training through value and Jacobian-vector products (tcnn_module_forward_jvp / tcnn_module_backward_jvp): what
 	// inference_jvp serves, on AoS matrices, in batches of 256, with at most 3 directions (1 at width 128)
 	void refuse_jvp_train(const std::string& front = "", const std::string& why = "") const {
@@ -387,6 +396,26 @@ struct ModuleNWIEF32 : ModuleBase {
 		if (!n) return;
 		TCNN_CHECK(in && out && jvp && params, "inference_jvp needs the input, the output, the product and the parameters");
 		model.jvp(st, n, in, directions, n_directions, (const float*)params, (float*)out, jvp, F32Layouts(mask));
+	}
+	// inference_jvp with sum_k v_k^T H v_k per output in the same launch (beyond the reference): the Laplacian under null
+	// directions. second follows the output bit like the product.
+	void inference_jvp_second(hipStream_t st, uint32_t n, const float* in, const float* directions, uint32_t n_directions, void* out, float* jvp,
+	                          float* second, const void* params, uint32_t mask) override {
+		TCNN_CHECK(mask < 4, "inference_jvp_second: layouts takes TCNN_LAYOUT_SOA_INPUT and TCNN_LAYOUT_SOA_OUTPUT only");
+		if (!model.fused_ok()) refuse_jvp_second();
+		const EncodingHost::Part* lone = model.enc->lone_part();
+		if (!lone || (lone->kind != COMP_IDENTITY && lone->kind != COMP_GRID)) refuse_jvp_second(model.enc->name());
+		TCNN_CHECK(!model.has_sine(), name() + ": Sine has no backward from its forward value: inference_jvp_second serves the other eight "
+		                                       "activations (use inference for the value)");
+		const std::string why = model.jvp_second_refusal();
+		if (!why.empty()) refuse_jvp_second(lone->kind == COMP_GRID ? model.enc->name() : "", why);
+		TCNN_CHECK(n % 128 == 0, "inference_jvp_second: batch size must be a multiple of 128");
+		TCNN_CHECK(directions ? n_directions >= 1 : (n_directions == 0 || n_directions == model.n_input_dims),
+		           "inference_jvp_second: n_directions must be at least 1, or 0 or the input width with null directions (the unit vectors)");
+		if (!n) return;
+		TCNN_CHECK(in && out && jvp && second && params,
+		           "inference_jvp_second needs the input, the output, the product, the second-order sum and the parameters");
+		model.jvp_second(st, n, in, directions, n_directions, (const float*)params, (float*)out, jvp, second, F32Layouts(mask));
 	}
 	// The same call keeping a context, and its reverse pass: dL/dparams of a loss on the output and on the product
 	// (beyond the reference). AoS matrices only; null directions are the unit vectors and count as n_input_dims.
@@ -716,6 +745,15 @@ int tcnn_module_inference_jvp(tcnn_module* m, void* stream, uint32_t n, const fl
 		TCNN_CHECK(m && m->m, "inference_jvp: null module");
 		// an empty batch still answers for the module: a refusal does not depend on n
 		m->m->inference_jvp((hipStream_t)stream, n, in, directions, n_directions, out, jvp, params, layouts);
+	});
+}
+
+int tcnn_module_inference_jvp_second(tcnn_module* m, void* stream, uint32_t n, const float* in, const float* directions, uint32_t n_directions,
+                                     void* out, float* jvp, float* second, const void* params, uint32_t layouts) {
+	return guard([&] {
+		TCNN_CHECK(m && m->m, "inference_jvp_second: null module");
+		// an empty batch still answers for the module: a refusal does not depend on n
+		m->m->inference_jvp_second((hipStream_t)stream, n, in, directions, n_directions, out, jvp, second, params, layouts);
 	});
 }
 

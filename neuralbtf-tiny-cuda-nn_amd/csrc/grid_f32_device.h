@@ -126,6 +126,66 @@ __device__ __forceinline__ void level_tangent_f32(uint32_t gd, float scale, cons
 	}
 }
 
+// The second derivative of the interpolation weight with respect to the cell fraction, from pos_fract_d's fraction:
+// 6 - 12 v for Smoothstep, else 0
+__device__ __forceinline__ float pos_fract_dd(float x, float scale, Interp interp) {
+	float v = __builtin_fmaf(scale, x, 0.5f);
+	v -= floorf(v);
+	return interp == Interp::Smoothstep ? __builtin_fmaf(-12.0f, v, 6.0f) : 0.0f;
+}
+
+// u[f] = sum_{d, d'} M[d][d'] d^2(level's features) / dx_d dx_d' from the corners the value gathered, M symmetric (its
+// upper triangle is read):
+//   d = d' (diag; pdd = 0 otherwise): scale^2 pdd_d sum over the 2^(D-1) edges along d of (product of the other
+//     weights) (v_right - v_left), which is level_tangent_f32 with pdd in the place of pd, times the scale;
+//   d < d' (mixed), counted twice: scale^2 pd_d pd_d' sum over the 2^(D-2) faces of (the remaining weight)
+//     (v_11 - v_10 - v_01 + v_00).
+// diag and mixed are wave-uniform: the interpolation, and whether the call has directions.
+template <uint32_t D, uint32_t NF>
+__device__ __forceinline__ void level_second_f32(float scale, const float* p, const float* pd, const float* pdd, const FVec<NF>* v,
+                                                 const float (&M)[D][D], bool diag, bool mixed, float* u) {
+	static_assert(D == 2 || D == 3, "a face has at most one dimension beside its two");
+#pragma unroll
+	for (uint32_t f = 0; f < NF; ++f) u[f] = 0.0f;
+	if (diag) {
+#pragma unroll
+		for (uint32_t d = 0; d < D; ++d) {
+			float g[NF];
+			level_tangent_f32<D, NF>(d, scale, p, pdd, v, g);
+			const float m = M[d][d] * scale;
+#pragma unroll
+			for (uint32_t f = 0; f < NF; ++f) u[f] = __builtin_fmaf(m, g[f], u[f]);
+		}
+	}
+	if (mixed) {
+#pragma unroll
+		for (uint32_t d = 0; d < D; ++d)
+#pragma unroll
+			for (uint32_t e = d + 1; e < D; ++e) {
+				float g[NF];
+#pragma unroll
+				for (uint32_t f = 0; f < NF; ++f) g[f] = 0.0f;
+#pragma unroll
+				for (uint32_t idx = 0; idx < (1u << (D - 2)); ++idx) {
+					float w = 1.0f;
+					uint32_t c00 = 0;
+#pragma unroll
+					for (uint32_t m = 0; m < D; ++m) {  // the dimensions beside d and e: one for D = 3, none for D = 2
+						if (m == d || m == e) continue;
+						if (idx == 0) w *= 1.0f - p[m];
+						else { w *= p[m]; c00 |= 1u << m; }
+					}
+					const uint32_t c10 = c00 | (1u << d), c01 = c00 | (1u << e), c11 = c10 | c01;
+#pragma unroll
+					for (uint32_t f = 0; f < NF; ++f) g[f] = __builtin_fmaf(w, (v[c11].v[f] - v[c10].v[f]) - (v[c01].v[f] - v[c00].v[f]), g[f]);
+				}
+				const float m = 2.0f * M[d][e] * ((scale * pd[d]) * (scale * pd[e]));
+#pragma unroll
+				for (uint32_t f = 0; f < NF; ++f) u[f] = __builtin_fmaf(m, g[f], u[f]);
+			}
+	}
+}
+
 // One level of one point (reference kernel_grid with T = float, grid.h:93-168): fp32 weight products in
 // the reference's order and one fp32 FMA per corner and feature, corners in the reference's order.
 template <uint32_t D, uint32_t F, HashType H>

@@ -510,7 +510,15 @@ bool f32_mlp_jvp_grid_ok(uint32_t D, uint32_t F, uint32_t IN);
 void launch_f32_mlp_jvp(hipStream_t st, uint32_t B, uint32_t D, uint32_t IN, uint32_t W, uint32_t NH, uint32_t OUTP, uint32_t n_out,
                         const float* params, const float* x, const float* directions, uint32_t n_directions, bool x_soa, float* y, float* jvp,
                         bool y_soa, int act, int out_act, const GridCall* grid, const float* table, float scale, float offset);
-// Training through that call (mlp_f32_jvp_train.hip): dL/dparams of a loss L(y, Jv). AoS only, B a multiple of 256,
+// That call with the summed second directional derivatives, the forward Laplacian (mlp_f32_jvp2.hip): y and jvp as
+// above, to the bit, and second[b][o] = sum_k v_k^T (d^2 y_o / dx^2) v_k, [B][n_out]; y_soa: [n_out][B]. Null
+// directions: jvp is the Jacobian and second the Laplacian. The same modules and the same argument checks, at the widths
+// f32_mlp_jvp2_width_ok: 16, 32 and 64 (the chain with the extra row does not fit the registers at 128).
+bool f32_mlp_jvp2_width_ok(uint32_t W);
+void launch_f32_mlp_jvp2(hipStream_t st, uint32_t B, uint32_t D, uint32_t IN, uint32_t W, uint32_t NH, uint32_t OUTP, uint32_t n_out,
+                         const float* params, const float* x, const float* directions, uint32_t n_directions, bool x_soa, float* y, float* jvp,
+                         float* second, bool y_soa, int act, int out_act, const GridCall* grid, const float* table, float scale, float offset);
+// Training through launch_f32_mlp_jvp (mlp_f32_jvp_train.hip): dL/dparams of a loss L(y, Jv). AoS only, B a multiple of 256,
 // K = n_directions <= f32_mlp_jvp_train_max_directions(W) (3 up to W 64, 1 at W 128), so the forward is one pass.
 uint32_t f32_mlp_jvp_train_max_directions(uint32_t W);
 // The context of the keeping forward, nq = 1 + K: X_0 [nq][B][IN] | X_1 .. X_NH [nq][B][W] | y [B][OUTP] | S_0 ..

@@ -162,5 +162,83 @@ __device__ __forceinline__ void jvp_encode_step(const JvpArgs& a, uint32_t s, ui
 	}
 }
 
+// The forward Laplacian's argument (mlp_f32_jvp2.hip): the call above and where sum_k v_k^T H v_k goes
+struct Jvp2Args {
+	JvpArgs j;
+	float* Q;  // [B][NOUT], or [NOUT][B] when y_soa
+};
+
+// jvp_encode_step with the second-order operand: e[0] the value and e[1 .. NQ - 2] the tangents, the operations of
+// jvp_encode_step in its order, and e[NQ - 1] the column's sum_{d, d'} M[d][d'] d^2 e / dx_d dx_d' with
+// M = sum_{k in pass} v_k v_k^T (level_second_f32), from the same corners: no second gather. The term is skipped where
+// it is exactly zero -- Nearest, and Linear with the unit directions -- and is zero on the padding columns.
+template <uint32_t D, uint32_t F, int NQ>
+__device__ __forceinline__ void jvp2_encode_step(const JvpArgs& a, uint32_t s, uint32_t q, uint32_t k0, const float (&x)[D],
+                                                 const float (&dir)[NQ - 2][D], const float (&M)[D][D], const uint32_t (&prime)[D],
+                                                 f4 (&e)[NQ]) {
+	constexpr uint32_t NF = F == 2 ? 2 : 4, NLV = 4 / NF, NC = 1u << D;
+	const Interp interp = (Interp)a.interp;
+	const bool vec = a.vec != 0, hash_grid = a.hash_grid != 0;
+	const bool diag = interp == Interp::Smoothstep, mixed = interp != Interp::Nearest && a.V != nullptr;
+	LevelInfo li[NLV];
+	bool on[NLV];
+	uint32_t f0[NLV];
+	float p[NLV][D], pd[NLV][D], pdd[NLV][D], w[NLV][NC];
+	FVec<NF> v[NLV][NC];
+#pragma unroll
+	for (uint32_t u = 0; u < NLV; ++u) {
+		const uint32_t col = 16 * s + 4 * q + u * NF, level = col / F;
+		f0[u] = col % F;
+		on[u] = level < a.L;
+		li[u] = a.levels[on[u] ? level : a.L - 1];
+		uint32_t pg[D];
+#pragma unroll
+		for (uint32_t d = 0; d < D; ++d) {
+			pos_fract_d(x[d], li[u].scale, interp, p[u][d], pd[u][d], pg[d]);
+			pdd[u][d] = pos_fract_dd(x[d], li[u].scale, interp);
+		}
+		const LevelInfo& l = li[u];
+		auto index = [&](const uint32_t* local) { return grid_index_primes<D>(hash_grid, l.size, l.res, local, prime); };
+		if (interp == Interp::Nearest) v[u][0] = load_fvec<NF>(a.table + (size_t)(l.offset + index(pg)) * F + f0[u], vec);
+		else gather_level_f32<D, F, NF>(a.table, l, p[u], pg, f0[u], vec, index, w[u], v[u]);
+	}
+#pragma unroll
+	for (uint32_t u = 0; u < NLV; ++u) {
+		if (interp == Interp::Nearest) {
+#pragma unroll
+			for (uint32_t f = 0; f < NF; ++f) {
+				e[0][u * NF + f] = on[u] ? v[u][0].v[f] : 0.0f;
+#pragma unroll
+				for (int i = 1; i < NQ; ++i) e[i][u * NF + f] = 0.0f;
+			}
+			continue;
+		}
+		float val[NF], g[D][NF], u2[NF];
+		combine_level_f32<NC, NF>(w[u], v[u], val);
+#pragma unroll
+		for (uint32_t gd = 0; gd < D; ++gd) level_tangent_f32<D, NF>(gd, li[u].scale, p[u], pd[u], v[u], g[gd]);
+		level_second_f32<D, NF>(li[u].scale, p[u], pd[u], pdd[u], v[u], M, diag, mixed, u2);
+#pragma unroll
+		for (uint32_t f = 0; f < NF; ++f) {
+			e[0][u * NF + f] = on[u] ? val[f] : 0.0f;
+#pragma unroll
+			for (int i = 1; i < NQ - 1; ++i) {
+				float t = 0.0f;
+				if (!a.V) {
+#pragma unroll
+					for (uint32_t d = 0; d < D; ++d)
+						if (k0 + (i - 1) == d) t = g[d][f];
+				} else {
+					t = g[0][f] * dir[i - 1][0];
+#pragma unroll
+					for (uint32_t d = 1; d < D; ++d) t = __builtin_fmaf(g[d][f], dir[i - 1][d], t);
+				}
+				e[i][u * NF + f] = on[u] ? t : 0.0f;
+			}
+			e[NQ - 1][u * NF + f] = on[u] ? u2[f] : 0.0f;
+		}
+	}
+}
+
 }  // namespace
 }  // namespace tcnn_amd

@@ -561,6 +561,13 @@ struct NetworkF32Host {
 	std::string jvp_refusal() const;
 	void jvp(hipStream_t st, uint32_t B, const float* x, const float* directions, uint32_t n_directions, const float* params, float* y,
 	         float* Jv, F32Layouts lay = {});
+	// jvp() with the summed second directional derivatives in the same launch (mlp_f32_jvp2.hip): y and Jv carry jvp()'s
+	// bits and second[b][o] = sum_k v_k^T (d^2 y_o / dx^2) v_k, [B][n_output_dims]; lay.output: [n_output_dims][B]. Null
+	// directions give the Jacobian and the Laplacian. Served when jvp_second_refusal() is empty: jvp_refusal(), and a
+	// width of 16, 32 or 64 (at 128 the chain with the extra row spills to scratch).
+	std::string jvp_second_refusal() const;
+	void jvp_second(hipStream_t st, uint32_t B, const float* x, const float* directions, uint32_t n_directions, const float* params, float* y,
+	                float* Jv, float* second, F32Layouts lay = {});
 	// Training through jvp() (mlp_f32_jvp_train.hip): dL/dparams of a loss L(y, Jv). jvp_forward is jvp() on AoS
 	// matrices, the same bits in y and Jv, and fills keep (jvp_keep_floats(B, K) floats; K counts the unit vectors as
 	// n_input_dims). jvp_backward takes dL_dy [B][padded_output] and dL_dJv [B][n_output_dims][K] (either null: zero, not

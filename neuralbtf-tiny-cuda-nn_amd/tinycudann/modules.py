@@ -254,6 +254,24 @@ class _NativeModule:
                                                   _ptr(out), _ptr(jv), _ptr(params), 3 if soa else 0))
         return out, jv
 
+    def jvp_second(self, input, directions, params, n_out, soa):
+        """tcnn_module_inference_jvp_second: jvp() and second [B, n_out] (soa: [n_out, B]) =
+        sum_k v_k^T (d^2 output / d input^2) v_k in the same launch"""
+        assert input.dtype == torch.float32 and input.is_contiguous() and input.shape[0 if soa else 1] == self._n_in
+        assert params.dtype == self._param_dtype and params.numel() == self._n_params
+        B, D, dev = input.shape[1 if soa else 0], self._n_in, input.device
+        K = D if directions is None else directions.shape[0 if soa else 1]
+        if directions is not None:
+            assert directions.dtype == torch.float32 and directions.is_contiguous()
+            assert tuple(directions.shape) == ((K, D, B) if soa else (B, K, D))
+        out = torch.empty((n_out, B) if soa else (B, self._n_out), dtype=self._out_dtype, device=dev)
+        jv = torch.empty((n_out, K, B) if soa else (B, n_out, K), dtype=torch.float32, device=dev)
+        second = torch.empty((n_out, B) if soa else (B, n_out), dtype=torch.float32, device=dev)
+        L.check(L.lib().tcnn_module_inference_jvp_second(self.h, _stream(input), B, _ptr(input), _ptr(directions),
+                                                         0 if directions is None else K, _ptr(out), _ptr(jv), _ptr(second), _ptr(params),
+                                                         3 if soa else 0))
+        return out, jv, second
+
     def fwd_jvp(self, input, directions, params, n_out):
         """tcnn_module_forward_jvp: jvp() on AoS matrices, keeping a context for bwd_jvp"""
         B, D = input.shape[0], self._n_in
@@ -582,6 +600,53 @@ class Module(torch.nn.Module):
             if soa:
                 return (y, jac) if batch_size == padded else (y[:, :batch_size], jac[:, :, :batch_size])
             return y[:batch_size, :self.n_output_dims], jac[:batch_size]
+
+    def value_jvp_and_second(self, x, v=None, layout="aos"):
+        """value_and_jvp and the summed second directional derivatives, in one forward-mode launch that keeps nothing
+        (tcnn_module_inference_jvp_second, the "forward Laplacian"):
+        layout="aos": x [B, n_input_dims], v [B, K, n_input_dims] -> (y [B, n_output_dims], Jv [B, n_output_dims, K],
+                      q [B, n_output_dims]);
+        layout="soa": x [n_input_dims, B], v [K, n_input_dims, B] -> (y [n_output_dims, B], Jv [n_output_dims, K, B],
+                      q [n_output_dims, B]),
+        with q[b, o] = sum_k v[b, k]^T (d^2 y_o / dx^2) v[b, k]; y and Jv are value_and_jvp's bits. A v of [B, D] ([D, B])
+        is one direction, K = 1: q is the curvature along it and Jv drops the K axis. v=None: the unit vectors, Jv the
+        Jacobian and q the Laplacian. Inference only, as value_and_jacobian; served by the modules it serves."""
+        if layout not in ("aos", "soa"):
+            raise ValueError(f"layout must be 'aos' or 'soa', got {layout!r}")
+        if v is not None and v.dim() not in (2, 3):
+            raise ValueError(f"v must be [B, D] or [B, K, D] ([D, B] or [K, D, B] for layout='soa'), got {tuple(v.shape)}")
+        soa = layout == "soa"
+        one = v is not None and v.dim() == 2
+        if one:
+            v = v.unsqueeze(0 if soa else 1)
+        with torch.no_grad():
+            if not x.is_cuda:
+                warnings.warn("input must be a CUDA tensor, but isn't. This indicates suboptimal performance.")
+                x = x.cuda()
+            batch_size = x.shape[1 if soa else 0]
+            if v is not None and v.shape[2 if soa else 0] != batch_size:
+                raise ValueError(f"v has another batch size than x: {tuple(v.shape)}")
+            g = _granularity()
+            padded = (batch_size + g - 1) // g * g
+
+            def prepare(t):
+                if batch_size != padded:
+                    t = torch.nn.functional.pad(t, [0, padded - batch_size] if soa else [0, 0] * (t.dim() - 1) + [0, padded - batch_size])
+                return t.to(torch.float).contiguous()
+
+            params = self.params.detach().to(self.native_tcnn_module._param_dtype).contiguous()
+            y, jv, q = self.native_tcnn_module.jvp_second(prepare(x), None if v is None else prepare(v.to(x.device)), params,
+                                                          self.n_output_dims, soa)
+            if soa:
+                y, jv, q = y[:, :batch_size], jv[:, :, :batch_size], q[:, :batch_size]
+            else:
+                y, jv, q = y[:batch_size, :self.n_output_dims], jv[:batch_size], q[:batch_size]
+            return y, (jv.squeeze(1 if soa else 2) if one else jv), q
+
+    def value_jacobian_and_laplacian(self, x, layout="aos"):
+        """value_jvp_and_second with the unit vectors: (y, J [B, n_output_dims, n_input_dims], the Laplacian
+        sum_d d^2 y_o / dx_d^2 [B, n_output_dims]); layout="soa": J [n_output_dims, n_input_dims, B], [n_output_dims, B]"""
+        return self.value_jvp_and_second(x, None, layout)
 
     def __getstate__(self):
         """modules.py:194-199: pickle everything except the native module (a C-ABI handle)."""
