@@ -193,6 +193,26 @@ tcnn_context* tcnn_module_forward_jvp(tcnn_module* m, void* stream, uint32_t n, 
 int tcnn_module_backward_jvp(tcnn_module* m, void* stream, const tcnn_context* ctx, uint32_t n, const void* dL_doutput,
                              const float* dL_djvp, void* dL_dparams, const float* input, const float* directions,
                              const void* params);
+/* Training through tcnn_module_inference_jvp_second (beyond the reference): dL/dparams of a loss L(output, jvp, second),
+ * a Poisson or Helmholtz residual or a curvature term among them, in one keeping forward and one reverse pass.
+ * tcnn_module_forward_jvp_second is tcnn_module_inference_jvp_second on AoS matrices (layouts 0), the same bits in
+ * output, jvp and second, and returns a context that holds the value's, every tangent's and the second-order sum's row
+ * of every layer. tcnn_module_backward_jvp_second takes dL_doutput and dL_djvp as tcnn_module_backward_jvp does and
+ * dL_dsecond, fp32 [n][n_output_dims] like second. Any of the three may be NULL, meaning zero; a call with all three
+ * NULL fails. dL_dparams, the context rule, reproducibility and what is not produced are tcnn_module_backward_jvp's.
+ * Of directions that differ from the forward's only one case is detected and refused: a forward with n_directions other
+ * than n_input_dims and a backward with NULL directions. Any other differing pointer is read as n_directions of the
+ * forward's and, by the context rule, runs the forward again.
+ * Served: the modules tcnn_module_inference_jvp_second serves (widths 16, 32 and 64), n a multiple of 256, at most 3
+ * directions (NULL directions count as n_input_dims). Anything else answers "<name>[ behind <encoding>]:
+ * forward_jvp_second / backward_jvp_second are not implemented by the MI355X engine yet (fp32 FullyFusedMLP network
+ * modules of width 16, 32 or 64 alone, behind a lone Identity encoding or behind a lone grid encoding only; AoS
+ * matrices, batches of 256, at most 3 directions)[: <what is not served>]". */
+tcnn_context* tcnn_module_forward_jvp_second(tcnn_module* m, void* stream, uint32_t n, const float* input, const float* directions,
+                                             uint32_t n_directions, void* output, float* jvp, float* second, const void* params);
+int tcnn_module_backward_jvp_second(tcnn_module* m, void* stream, const tcnn_context* ctx, uint32_t n, const void* dL_doutput,
+                                    const float* dL_djvp, const float* dL_dsecond, void* dL_dparams, const float* input,
+                                    const float* directions, const void* params);
 /* The torch binding's backward with its loss-scale arithmetic folded in (reference
  * bindings/torch/tinycudann/modules.py:128-138): dL_doutput (fp16) is multiplied by loss_scale and
  * rounded to fp16, the module's backward runs on it, dL_dinput (fp32) is divided by loss_scale and

@@ -116,6 +116,16 @@ public:
 	virtual void backward_jvp(hipStream_t, const Context&, uint32_t, const void*, const float*, void*, const float*, const float*, const void*) {
 		throw std::runtime_error(name() + ": backward_jvp is not implemented");
 	}
+	// Beyond the reference: inference_jvp_second keeping a context, and its reverse pass, dL_dparams of a loss on the
+	// output, the product and the second-order sum (tcnn_module_forward_jvp_second / tcnn_module_backward_jvp_second).
+	// Any of dL_doutput, dL_djvp and dL_dsecond may be null (zero), not all three.
+	virtual Context forward_jvp_second(hipStream_t, uint32_t, const float*, const float*, uint32_t, void*, float*, float*, const void*) {
+		throw std::runtime_error(name() + ": forward_jvp_second is not implemented");
+	}
+	virtual void backward_jvp_second(hipStream_t, const Context&, uint32_t, const void*, const float*, const float*, void*, const float*,
+	                                 const float*, const void*) {
+		throw std::runtime_error(name() + ": backward_jvp_second is not implemented");
+	}
 
 	virtual uint32_t n_input_dims() const = 0;
 	virtual uint32_t n_output_dims() const = 0;
@@ -181,6 +191,17 @@ public:
 	void backward_jvp(hipStream_t stream, const Context& ctx, uint32_t n, const void* dL_doutput, const float* dL_djvp, void* dL_dparams,
 	                  const float* input, const float* directions, const void* params) override {
 		check(tcnn_module_backward_jvp(m_h, stream, native(ctx), n, dL_doutput, dL_djvp, dL_dparams, input, directions, params));
+	}
+	Context forward_jvp_second(hipStream_t stream, uint32_t n, const float* input, const float* directions, uint32_t n_directions,
+	                           void* output, float* jvp, float* second, const void* params) override {
+		tcnn_context* c = check_ptr(tcnn_module_forward_jvp_second(m_h, stream, n, input, directions, n_directions, output, jvp, second, params));
+		return Context{std::make_unique<NativeContext>(c)};
+	}
+	void backward_jvp_second(hipStream_t stream, const Context& ctx, uint32_t n, const void* dL_doutput, const float* dL_djvp,
+	                         const float* dL_dsecond, void* dL_dparams, const float* input, const float* directions,
+	                         const void* params) override {
+		check(tcnn_module_backward_jvp_second(m_h, stream, native(ctx), n, dL_doutput, dL_djvp, dL_dsecond, dL_dparams, input, directions,
+		                                      params));
 	}
 	uint32_t n_input_dims() const override { return tcnn_module_n_input_dims(m_h); }
 	uint32_t n_output_dims() const override { return tcnn_module_n_output_dims(m_h); }

@@ -69,6 +69,33 @@ __device__ __forceinline__ float act_factor2_f32(int a, float y) {
 	}
 }
 
+// d^3 act / d z^3 in the forward value y: what the reverse pass of the forward Laplacian needs beside the two above.
+// Zero for None, ReLU and LeakyReLU. With phi = act_factor_f32: Sigmoid phi (1 - 6 phi), Tanh -2 phi (1 - 3 y^2);
+// Softplus K^2 (1 - e) e (2 e - 1) with e = exp(-K y); Squareplus 6 K^2 t^4 (1 - t^2) / (t^2 + 1)^5 with t = K y.
+__device__ __forceinline__ float act_factor3_f32(int a, float y) {
+	switch (a) {
+		case AF32_EXPONENTIAL: return y;
+		case AF32_SIGMOID: {
+			const float p = y * (1.0f - y);
+			return p * (1.0f - 6.0f * p);
+		}
+		case AF32_SQUAREPLUS: {
+			const float t = y * K_ACT_F32;
+			const float t2 = t * t, d = t2 + 1.0f, d2 = d * d;
+			return (6.0f * K_ACT_F32 * K_ACT_F32) * ((t2 * t2) * (1.0f - t2)) / ((d2 * d2) * d);
+		}
+		case AF32_SOFTPLUS: {
+			const float e = expf(-y * K_ACT_F32);
+			return (K_ACT_F32 * K_ACT_F32) * (((1.0f - e) * e) * (2.0f * e - 1.0f));
+		}
+		case AF32_TANH: {
+			const float y2 = y * y;
+			return (-2.0f * (1.0f - y2)) * (1.0f - 3.0f * y2);
+		}
+		default: return 0.0f;
+	}
+}
+
 __device__ __forceinline__ float act_bwd_f32(int a, float g, float y) {
 	if (a == AF32_NONE) return g;
 	if (a == AF32_RELU) return y > 0.0f ? g : 0.0f;

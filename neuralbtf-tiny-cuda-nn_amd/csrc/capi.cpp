@@ -163,6 +163,23 @@ struct ModuleBase {
 	virtual void backward_jvp(hipStream_t, const ModuleCtx*, uint32_t, const void*, const float*, void*, const float*, const float*, const void*) {
 		refuse_jvp_train();
 	}
+	// Training through the forward Laplacian (tcnn_module_forward_jvp_second / tcnn_module_backward_jvp_second): what
+	// inference_jvp_second serves, on AoS matrices, in batches of 256, with at most 3 directions
+	void refuse_jvp_second_train(const std::string& front = "", const std::string& why = "") const {
+		throw std::runtime_error(name() + (front.empty() ? "" : " behind " + front) +
+		                         ": forward_jvp_second / backward_jvp_second are not implemented by the MI355X engine yet (fp32 FullyFusedMLP "
+		                         "network modules of width 16, 32 or 64 alone, behind a lone Identity encoding or behind a lone grid encoding "
+		                         "only; AoS matrices, batches of 256, at most 3 directions)" + (why.empty() ? "" : ": " + why));
+	}
+	virtual std::unique_ptr<ModuleCtx> forward_jvp_second(hipStream_t, uint32_t, const float*, const float*, uint32_t, void*, float*, float*,
+	                                                      const void*) {
+		refuse_jvp_second_train();
+		return nullptr;
+	}
+	virtual void backward_jvp_second(hipStream_t, const ModuleCtx*, uint32_t, const void*, const float*, const float*, void*, const float*,
+	                                 const float*, const void*) {
+		refuse_jvp_second_train();
+	}
 	virtual GridEncodingHost* grid_encoding() { return nullptr; }
 	// precision of the parameters, the output, dL/doutput and dL/dparams (TCNN_PRECISION_*): fp16 for
 	// every module but an encoding or a network created with Fp32
@@ -481,6 +498,75 @@ struct ModuleNWIEF32 : ModuleBase {
 		}
 		model.jvp_backward(st, n, in, directions, c->K, (const float*)params, (const float*)dL_dout, dL_djvp, keep, (float*)dL_dparams);
 	}
+	// The forward Laplacian keeping a context, and its reverse pass: dL/dparams of a loss on the output, the product and
+	// the second-order sum (beyond the reference). The rules of forward_jvp / backward_jvp; a context type of its own, so
+	// that neither backward takes the other forward's context.
+	struct Jvp2Ctx : ModuleCtx {
+		std::shared_ptr<KeepPool> pool;
+		std::unique_ptr<DevBuf> keep;
+		const float* in = nullptr;
+		const float* directions = nullptr;
+		const void* params = nullptr;
+		uint32_t K = 0;
+		~Jvp2Ctx() override {
+			if (pool && keep) pool->put(std::move(keep));
+		}
+	};
+	uint32_t check_jvp_second_train(uint32_t n, const float* directions, uint32_t n_directions) const {
+		if (!model.fused_ok()) refuse_jvp_second_train();
+		const EncodingHost::Part* lone = model.enc->lone_part();
+		if (!lone || (lone->kind != COMP_IDENTITY && lone->kind != COMP_GRID)) refuse_jvp_second_train(model.enc->name());
+		TCNN_CHECK(directions ? n_directions >= 1 : (n_directions == 0 || n_directions == model.n_input_dims),
+		           "forward_jvp_second: n_directions must be at least 1, or 0 or the input width with null directions (the unit vectors)");
+		const uint32_t K = directions ? n_directions : model.n_input_dims;
+		const std::string why = model.jvp_second_train_refusal(n, K);
+		if (!why.empty()) refuse_jvp_second_train(model.enc->name(), why);
+		return K;
+	}
+	std::unique_ptr<ModuleCtx> forward_jvp_second(hipStream_t st, uint32_t n, const float* in, const float* directions, uint32_t n_directions,
+	                                              void* out, float* jvp, float* second, const void* params) override {
+		const uint32_t K = check_jvp_second_train(n, directions, n_directions);
+		check_batch(n);
+		auto c = std::make_unique<Jvp2Ctx>();
+		c->K = K;
+		if (!n) return c;
+		TCNN_CHECK(in && out && jvp && second && params,
+		           "forward_jvp_second needs the input, the output, the product, the second-order sum and the parameters");
+		c->pool = pool;
+		c->keep = pool->get();
+		c->keep->reserve(model.jvp_second_keep_floats(n, K) * 4);
+		model.jvp_second_forward(st, n, in, directions, K, (const float*)params, (float*)out, jvp, second, c->keep->as<float>());
+		c->in = in;
+		c->directions = directions;
+		c->params = params;
+		return c;
+	}
+	void backward_jvp_second(hipStream_t st, const ModuleCtx* ctx, uint32_t n, const void* dL_dout, const float* dL_djvp, const float* dL_dsecond,
+	                         void* dL_dparams, const float* in, const float* directions, const void* params) override {
+		const Jvp2Ctx* c = dynamic_cast<const Jvp2Ctx*>(ctx);
+		TCNN_CHECK(c, "backward_jvp_second: the context does not come from forward_jvp_second");
+		TCNN_CHECK(dL_dout || dL_djvp || dL_dsecond,
+		           "backward_jvp_second: dL_doutput, dL_djvp and dL_dsecond are all null: there is nothing to differentiate");
+		if (!directions && c->K != model.n_input_dims)
+			refuse_jvp_second_train(model.enc->name(), "the forward ran " + std::to_string(c->K) + " directions and the backward was given none (null "
+			                                           "directions are the " + std::to_string(model.n_input_dims) +
+			                                           " unit vectors): pass the forward's directions");
+		check_jvp_second_train(n, directions, directions ? c->K : 0);
+		check_batch(n);
+		if (!n || !dL_dparams) return;
+		TCNN_CHECK(in && params, "backward_jvp_second needs the input and the parameters");
+		const float* keep = c->keep ? c->keep->as<float>() : nullptr;
+		if (!keep || c->in != in || c->directions != directions || c->params != params) {
+			const size_t nk = model.jvp_second_keep_floats(n, c->K), ny = (size_t)n * model.mlp.padded_output;
+			rekeep.reserve((nk + ny + (size_t)n * model.n_output_dims * (c->K + 1)) * 4);
+			float* y = rekeep.as<float>() + nk;
+			model.jvp_second_forward(st, n, in, directions, c->K, (const float*)params, y, y + ny, y + ny + (size_t)n * model.n_output_dims * c->K,
+			                         rekeep.as<float>());
+			keep = rekeep.as<float>();
+		}
+		model.jvp_second_backward(st, n, in, directions, c->K, (const float*)params, (const float*)dL_dout, dL_djvp, dL_dsecond, keep,
+		                          (float*)dL_dparams);
+	}
 	GridEncodingHost* grid_encoding() override { return model.enc->lone_grid(); }
 	// "fused" / "chain": the whole network in one launch (mlp_f32_fused.hip); the weight gradients stay per layer
 	const char* engine() const override { return model.fused_ok() ? "fused" : "layered"; }
@@ -776,6 +862,29 @@ int tcnn_module_backward_jvp(tcnn_module* m, void* stream, const tcnn_context* c
 		TCNN_CHECK(ctx != nullptr, "backward_jvp: null context");
 		TCNN_CHECK(ctx->n == n, "backward_jvp: batch size differs from the forward's");
 		m->m->backward_jvp((hipStream_t)stream, ctx->impl.get(), n, dL_dout, dL_djvp, dL_dparams, in, directions, params);
+		if (n == 0 && dL_dparams) TCNN_HIP_CHECK(hipMemsetAsync(dL_dparams, 0, m->m->n_params() * m->m->elem_bytes(), (hipStream_t)stream));
+	});
+}
+
+tcnn_context* tcnn_module_forward_jvp_second(tcnn_module* m, void* stream, uint32_t n, const float* in, const float* directions,
+                                             uint32_t n_directions, void* out, float* jvp, float* second, const void* params) {
+	return guard_ptr<tcnn_context>([&] {
+		TCNN_CHECK(m && m->m, "forward_jvp_second: null module");
+		auto c = std::make_unique<tcnn_context>();
+		c->n = n;
+		// an empty batch still answers for the module: a refusal does not depend on n
+		c->impl = m->m->forward_jvp_second((hipStream_t)stream, n, in, directions, n_directions, out, jvp, second, params);
+		return c.release();
+	});
+}
+
+int tcnn_module_backward_jvp_second(tcnn_module* m, void* stream, const tcnn_context* ctx, uint32_t n, const void* dL_dout, const float* dL_djvp,
+                                    const float* dL_dsecond, void* dL_dparams, const float* in, const float* directions, const void* params) {
+	return guard([&] {
+		TCNN_CHECK(m && m->m, "backward_jvp_second: null module");
+		TCNN_CHECK(ctx != nullptr, "backward_jvp_second: null context");
+		TCNN_CHECK(ctx->n == n, "backward_jvp_second: batch size differs from the forward's");
+		m->m->backward_jvp_second((hipStream_t)stream, ctx->impl.get(), n, dL_dout, dL_djvp, dL_dsecond, dL_dparams, in, directions, params);
 		if (n == 0 && dL_dparams) TCNN_HIP_CHECK(hipMemsetAsync(dL_dparams, 0, m->m->n_params() * m->m->elem_bytes(), (hipStream_t)stream));
 	});
 }

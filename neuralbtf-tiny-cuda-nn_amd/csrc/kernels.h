@@ -542,6 +542,29 @@ void launch_f32_mlp_jvp_bwd_chain(hipStream_t st, uint32_t B, uint32_t IN, uint3
 // gradient. directions [B][K][D], null: the unit vectors (K = D); t0 [K][B][IN]. Nearest: nothing to add.
 void launch_grid_jvp_bwd_f32(hipStream_t st, const GridCall& g, uint32_t B, uint32_t K, uint32_t IN, const float* x, const float* directions,
                              const float* t0, float* grad);
+// Training through launch_f32_mlp_jvp2 (mlp_f32_jvp2_train.hip): dL/dparams of a loss L(y, Jv, q). AoS only, B a multiple
+// of 256, widths 16, 32 and 64, K = n_directions <= f32_mlp_jvp2_train_max_directions(W) (3; 0 at a width not served).
+uint32_t f32_mlp_jvp2_train_max_directions(uint32_t W);
+// The context and the stack above with nq = 2 + K: X_j = (h_j, t_{j,1..K}, U_j), S_j = (s_{j,1..K}, r_j) and
+// G_j = (zb_j, sb_{j,1..K}, rb_j), then (hb_0, tb_{0,1..K}, Ub_0). Behind an Identity U_0 = 0 is not written.
+size_t f32_mlp_jvp2_keep_floats(uint32_t B, uint32_t K, uint32_t IN, uint32_t W, uint32_t NH, uint32_t OUTP);
+size_t f32_mlp_jvp2_stack_floats(uint32_t B, uint32_t K, uint32_t IN, uint32_t W, uint32_t NH, uint32_t OUTP);
+size_t f32_mlp_jvp2_keep_x(uint32_t B, uint32_t K, uint32_t IN, uint32_t W, uint32_t NH, uint32_t OUTP, uint32_t j);   // X_j, j <= NH
+size_t f32_mlp_jvp2_stack_g(uint32_t B, uint32_t K, uint32_t IN, uint32_t W, uint32_t NH, uint32_t OUTP, uint32_t j);  // G_j; j = NH + 1: hb_0
+// launch_f32_mlp_jvp2 on AoS matrices, with the same bits in y, jvp and second, writing the context
+void launch_f32_mlp_jvp2_keep(hipStream_t st, uint32_t B, uint32_t D, uint32_t IN, uint32_t W, uint32_t NH, uint32_t OUTP, uint32_t n_out,
+                              const float* params, const float* x, const float* directions, uint32_t n_directions, float* y, float* jvp,
+                              float* second, int act, int out_act, const GridCall* grid, const float* table, float scale, float offset,
+                              float* keep);
+// from dL_dy [B][OUTP], dL_djvp [B][n_out][K] and dL_dsecond [B][n_out] (each nullable: zero, not all) down to the
+// encoded row, filling the stack; want_d0: also (hb_0, tb_0, Ub_0), which only an encoding with parameters reads
+void launch_f32_mlp_jvp2_bwd_chain(hipStream_t st, uint32_t B, uint32_t IN, uint32_t W, uint32_t NH, uint32_t OUTP, uint32_t n_out, uint32_t K,
+                                   const float* params, const float* keep, const float* dL_dy, const float* dL_djvp, const float* dL_dsecond,
+                                   float* stack, bool want_d0, int act, int out_act);
+// launch_grid_jvp_bwd_f32's term and grad[idx_c][f] += (sum_{d,d'} M[d][d'] d^2 w_c / dx_d dx_d') t0[K][b][l F + f],
+// M = sum_k v_k v_k^T, in one corner walk: the tangent and second-order terms of the table gradient. t0 [K + 1][B][IN].
+void launch_grid_jvp2_bwd_f32(hipStream_t st, const GridCall& g, uint32_t B, uint32_t K, uint32_t IN, const float* x, const float* directions,
+                              const float* t0, float* grad);
 // dst[C][R] = src[R][C]^T
 void launch_f32_transpose(hipStream_t st, uint32_t R, uint32_t C, const float* src, float* dst);
 

@@ -240,5 +240,45 @@ __device__ __forceinline__ void jvp2_encode_step(const JvpArgs& a, uint32_t s, u
 	}
 }
 
+// ---- shared by the kernels that train through these calls (mlp_f32_jvp_train.hip, mlp_f32_jvp2_train.hip) ----
+
+// f32_act_has_curvature (kernels.h) on the device: wave-uniform, so a network without curvature branches around S
+__device__ __forceinline__ bool act_has_curvature(int a) { return a != ACT_NONE && a != ACT_RELU && a != ACT_LEAKY_RELU && a != ACT_SINE; }
+
+// Where the pieces of a context lie (floats), nq quantities: 1 + K, the value and the tangents, or 2 + K with the
+// second-order sum last (S_j then holds r_j after the tangents)
+struct KeepLayout {
+	size_t B, nq, IN, W, NH, OUTP;
+	__host__ __device__ size_t x(uint32_t j) const { return j == 0 ? 0 : nq * B * IN + (size_t)(j - 1) * nq * B * W; }  // X_j, j <= NH
+	__host__ __device__ size_t y() const { return nq * B * (IN + NH * W); }
+	__host__ __device__ size_t s(uint32_t j) const { return y() + B * OUTP + (size_t)j * (nq - 1) * B * W; }  // S_j, j <= NH
+	__host__ __device__ size_t total() const { return s((uint32_t)NH) + (nq - 1) * B * OUTP; }
+	// the reverse chain's stack: G_j, j <= NH, then [hb_0 | tb_0] [nq][B][IN]
+	__host__ __device__ size_t g(uint32_t j) const { return (size_t)j * nq * B * W; }
+	__host__ __device__ size_t d0() const { return nq * B * (NH * W + OUTP); }
+	__host__ __device__ size_t stack_total() const { return d0() + nq * B * IN; }
+};
+
+// quantity i's f4 of row `row` at column col of a [.][B][width] block
+__device__ __forceinline__ float* slot(float* base, size_t B, uint32_t width, uint32_t i, uint32_t row, uint32_t col) {
+	return base + ((size_t)i * B + row) * width + col;
+}
+
+// acc[i][c] += W[16 s + 4 q + j][16 c + r] g[i][s][j]: bwd_from_regs (mlp_f32_fused.hip) for 1 + TG adjoints, each
+// weight used by all of them; wp = &W[4 q][r] of the first column tile, K the row length of W
+template <int WT, int NQ, int NC>
+__device__ __forceinline__ void jvp_bwd_from_regs(const float* __restrict__ wp, uint32_t K, const f4 (&g)[NQ][WT], f4 (&acc)[NQ][NC]) {
+#pragma unroll
+	for (int s = 0; s < WT; ++s)
+#pragma unroll
+		for (int c = 0; c < NC; ++c)
+#pragma unroll
+			for (int j = 0; j < 4; ++j) {
+				const float w = wp[(size_t)(16 * s + j) * K + 16 * c];
+#pragma unroll
+				for (int i = 0; i < NQ; ++i) acc[i][c] = mfma4(w, g[i][s][j], acc[i][c]);
+			}
+}
+
 }  // namespace
 }  // namespace tcnn_amd

@@ -1428,6 +1428,68 @@ void NetworkF32Host::jvp_backward(hipStream_t st, uint32_t B, const float* x, co
 	launch_f32_add(st, n_enc, dL_dparams + n_mlp, grid_tmp.as<float>());
 }
 
+std::string NetworkF32Host::jvp_second_train_refusal(uint32_t B, uint32_t K) const {
+	const std::string why = jvp_second_refusal();
+	if (!why.empty()) return why;
+	const uint32_t max_k = f32_mlp_jvp2_train_max_directions(mlp.width);
+	if (K < 1 || K > max_k)
+		return std::to_string(K) + " directions at width " + std::to_string(mlp.width) + " (at most " + std::to_string(max_k) +
+		       " are served; the unit vectors count as the input width)";
+	if (B % 256 != 0) return "a batch of " + std::to_string(B) + " (a multiple of 256 is served)";
+	return "";
+}
+
+size_t NetworkF32Host::jvp_second_keep_floats(uint32_t B, uint32_t K) const {
+	return f32_mlp_jvp2_keep_floats(B, K, mlp.n_input, mlp.width, mlp.n_hidden_layers, mlp.padded_output);
+}
+
+void NetworkF32Host::jvp_second_forward(hipStream_t st, uint32_t B, const float* x, const float* directions, uint32_t K, const float* params,
+                                        float* y, float* Jv, float* second, float* keep) {
+	const std::string why = jvp_second_train_refusal(B, K);
+	TCNN_CHECK(why.empty(), "fp32 network: no training through the forward Laplacian: " + why);
+	const EncodingHost::Part* p = enc->lone_part();
+	const GridCall gc = p->grid ? p->grid->call() : GridCall{};
+	launch_f32_mlp_jvp2_keep(st, B, n_input_dims, mlp.n_input, mlp.width, mlp.n_hidden_layers, mlp.padded_output, n_output_dims, params, x,
+	                         directions, K, y, Jv, second, mlp.activation, mlp.output_activation, p->grid ? &gc : nullptr,
+	                         p->grid ? params + mlp.n_params() + p->param_offset : nullptr, p->f0, p->f1, keep);
+}
+
+void NetworkF32Host::jvp_second_backward(hipStream_t st, uint32_t B, const float* x, const float* directions, uint32_t K, const float* params,
+                                         const float* dL_dy, const float* dL_dJv, const float* dL_dq, const float* keep, float* dL_dparams) {
+	const std::string why = jvp_second_train_refusal(B, K);
+	TCNN_CHECK(why.empty(), "fp32 network: no training through the forward Laplacian: " + why);
+	if (!B || !dL_dparams) return;
+	const uint32_t W = mlp.width, IN = mlp.n_input, NH = mlp.n_hidden_layers, OUTP = mlp.padded_output;
+	const uint32_t n_mlp = mlp.n_params(), n_enc = enc->n_params();
+	const GridEncodingHost* grid = enc->lone_grid();
+	jvp_stack.reserve(f32_mlp_jvp2_stack_floats(B, K, IN, W, NH, OUTP) * 4);
+	float* stack = jvp_stack.as<float>();
+	launch_f32_mlp_jvp2_bwd_chain(st, B, IN, W, NH, OUTP, n_output_dims, K, params, keep, dL_dy, dL_dJv, dL_dq, stack, grid != nullptr,
+	                              mlp.activation, mlp.output_activation);
+	// dW_j = G_j^T X_j over the (2 + K) B stacked rows, the gate already applied. Behind an Identity U_0 = 0 is not kept:
+	// the first layer runs over the 1 + K leading quantities, which lie first in G_0 and X_0 alike.
+	wgrad_partial.reserve((size_t)f32_wgrad_n_slabs((2 + K) * B) * std::max(W, OUTP) * std::max(W, IN) * 4);
+	for (uint32_t j = 0; j <= NH; ++j) {
+		const uint32_t N = j < NH ? W : OUTP, Kj = j == 0 ? IN : W;
+		const uint32_t rows = (j == 0 && !grid ? 1 + K : 2 + K) * B, nsl = f32_wgrad_n_slabs(rows);
+		const size_t off = j == 0 ? 0 : (size_t)W * IN + (size_t)(j - 1) * W * W;
+		launch_f32_wgrad(st, rows, N, Kj, stack + f32_mlp_jvp2_stack_g(B, K, IN, W, NH, OUTP, j), nullptr, ACT_NONE,
+		                 keep + f32_mlp_jvp2_keep_x(B, K, IN, W, NH, OUTP, j), wgrad_partial.as<float>());
+		const size_t tf = reduce_partials_tmp_floats(nsl, N * Kj);
+		if (tf) red_tmp.reserve(tf * 4);
+		launch_reduce_partials(st, wgrad_partial.as<float>(), nsl, N * Kj, N * Kj, dL_dparams + off, red_tmp.as<float>());
+	}
+	if (!grid) return;
+	// the table: w_c hb_0 through the first-order backward, then the tangent and second-order terms by atomics onto zeros
+	const float* hb0 = stack + f32_mlp_jvp2_stack_g(B, K, IN, W, NH, OUTP, NH + 1);
+	enc->backward_params(st, B, x, hb0, 2, dL_dparams + n_mlp);
+	if (grid->desc.interp == Interp::Nearest) return;
+	grid_tmp.reserve((size_t)n_enc * 4);
+	TCNN_HIP_CHECK(hipMemsetAsync(grid_tmp.p, 0, (size_t)n_enc * 4, st));
+	launch_grid_jvp2_bwd_f32(st, grid->call(), B, K, IN, x, directions, hb0 + (size_t)B * IN, grid_tmp.as<float>());
+	launch_f32_add(st, n_enc, dL_dparams + n_mlp, grid_tmp.as<float>());
+}
+
 const float* NetworkF32Host::aos_positions(hipStream_t st, uint32_t B, const float* pos_soa) {
 	pos_aos.reserve((size_t)B * n_input_dims * 4);
 	launch_f32_transpose(st, n_input_dims, B, pos_soa, pos_aos.as<float>());

@@ -581,7 +581,20 @@ struct NetworkF32Host {
 	                 float* keep);
 	void jvp_backward(hipStream_t st, uint32_t B, const float* x, const float* directions, uint32_t K, const float* params, const float* dL_dy,
 	                  const float* dL_dJv, const float* keep, float* dL_dparams);
-	DevBuf jvp_stack;  // grow-only scratch of jvp_backward: the reverse chain's adjoints
+	// Training through jvp_second() (mlp_f32_jvp2_train.hip): dL/dparams of a loss L(y, Jv, q). jvp_second_forward is
+	// jvp_second() on AoS matrices, the same bits in y, Jv and second, and fills keep (jvp_second_keep_floats(B, K)
+	// floats). jvp_second_backward takes dL_dy, dL_dJv as jvp_backward and dL_dq [B][n_output_dims] (each null: zero, not
+	// all three) and overwrites dL_dparams: one reverse-chain launch, one weight-gradient product per layer over the
+	// (2 + K) B stacked rows (1 + K behind an Identity's first layer, whose U is zero), and for a grid the value term
+	// through its first-order backward plus the tangent and second-order terms in one walk of fp32 atomics.
+	// Served when jvp_second_train_refusal(B, K) is empty: jvp_second_refusal(), B a multiple of 256, K <= 3.
+	std::string jvp_second_train_refusal(uint32_t B, uint32_t K) const;
+	size_t jvp_second_keep_floats(uint32_t B, uint32_t K) const;
+	void jvp_second_forward(hipStream_t st, uint32_t B, const float* x, const float* directions, uint32_t K, const float* params, float* y,
+	                        float* Jv, float* second, float* keep);
+	void jvp_second_backward(hipStream_t st, uint32_t B, const float* x, const float* directions, uint32_t K, const float* params,
+	                         const float* dL_dy, const float* dL_dJv, const float* dL_dq, const float* keep, float* dL_dparams);
+	DevBuf jvp_stack;  // grow-only scratch of jvp_backward and jvp_second_backward: the reverse chain's adjoints
 	const float* aos_positions(hipStream_t st, uint32_t B, const float* pos_soa);
 	DevBuf pos_aos, dy_aos, dx_aos;  // grow-only scratch of SoA calls
 	// Second order with respect to the input, from a forward's keep: dL_ddLdinput = dL2/d(dL/dinput) fp32

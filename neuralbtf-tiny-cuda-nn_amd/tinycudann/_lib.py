@@ -48,6 +48,9 @@ _SIGS = {
                                                  c_uint32]),
     "tcnn_module_forward_jvp": (c_void_p, [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p]),
     "tcnn_module_backward_jvp": (c_int, [c_void_p, c_void_p, c_void_p, c_uint32] + [c_void_p] * 6),
+    "tcnn_module_forward_jvp_second": (c_void_p, [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p,
+                                                  c_void_p]),
+    "tcnn_module_backward_jvp_second": (c_int, [c_void_p, c_void_p, c_void_p, c_uint32] + [c_void_p] * 7),
     "tcnn_module_forward_layout": (c_void_p, [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_int, c_uint32]),
     "tcnn_module_backward_layout": (c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                             c_uint32]),

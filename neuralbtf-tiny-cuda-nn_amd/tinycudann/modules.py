@@ -290,6 +290,26 @@ class _NativeModule:
                                                  _ptr(dL_dparams), _ptr(input), _ptr(directions), _ptr(params)))
         return dL_dparams
 
+    def fwd_jvp_second(self, input, directions, params, n_out):
+        """tcnn_module_forward_jvp_second: jvp_second() on AoS matrices, keeping a context for bwd_jvp_second"""
+        B, D = input.shape[0], self._n_in
+        K = D if directions is None else directions.shape[1]
+        out = torch.empty(B, self._n_out, dtype=self._out_dtype, device=input.device)
+        jv = torch.empty(B, n_out, K, dtype=torch.float32, device=input.device)
+        second = torch.empty(B, n_out, dtype=torch.float32, device=input.device)
+        ctx = L.check_ptr(L.lib().tcnn_module_forward_jvp_second(self.h, _stream(input), B, _ptr(input), _ptr(directions),
+                                                                  0 if directions is None else K, _ptr(out), _ptr(jv), _ptr(second),
+                                                                  _ptr(params)))
+        return _NativeContext(ctx), out, jv, second
+
+    def bwd_jvp_second(self, ctx, input, directions, params, dL_doutput, dL_djvp, dL_dsecond):
+        """tcnn_module_backward_jvp_second: dL_doutput [B, padded n_out], dL_djvp [B, n_out, K] and dL_dsecond [B, n_out]
+        (any None: zero) -> dL_dparams"""
+        dL_dparams = torch.empty(self._n_params, dtype=self._param_dtype, device=input.device)
+        L.check(L.lib().tcnn_module_backward_jvp_second(self.h, _stream(input), ctx.h, input.shape[0], _ptr(dL_doutput), _ptr(dL_djvp),
+                                                        _ptr(dL_dsecond), _ptr(dL_dparams), _ptr(input), _ptr(directions), _ptr(params)))
+        return dL_dparams
+
     def bwd_bwd_input(self, ctx, input, params, dL_ddLdinput, dL_doutput):
         """bindings.cpp:185-239: second-order gradients from dL/d(dL/dinput)."""
         B = input.shape[0]
@@ -446,6 +466,34 @@ class _jvp_function(torch.autograd.Function):
         return None, None, None, params_grad, None
 
 
+class _jvp_second_function(torch.autograd.Function):
+    """value_jvp_and_second / value_jacobian_and_laplacian with differentiable=True: the output, the product and the
+    second-order sum carry a graph to the parameters (tcnn_module_forward_jvp_second /
+    tcnn_module_backward_jvp_second). First order, parameters only."""
+
+    @staticmethod
+    def forward(ctx, native_tcnn_module, input, directions, params, n_out):
+        ctx.set_materialize_grads(False)
+        native_ctx, output, jv, second = native_tcnn_module.fwd_jvp_second(input, directions, params, n_out)
+        ctx.save_for_backward(input, params)
+        ctx.directions = directions
+        ctx.native_tcnn_module = native_tcnn_module
+        ctx.native_ctx = native_ctx
+        return output, jv, second
+
+    @staticmethod
+    def backward(ctx, doutput, djv, dsecond):
+        if torch.is_grad_enabled():
+            raise ValueError("value_jvp_and_second(differentiable=True) is differentiable once: a double backward through it "
+                             "(create_graph=True) is not implemented")
+        if doutput is None and djv is None and dsecond is None:
+            return None, None, None, None, None
+        input, params = ctx.saved_tensors
+        doutput, djv, dsecond = (None if t is None else t.to(torch.float32).contiguous() for t in (doutput, djv, dsecond))
+        params_grad = ctx.native_tcnn_module.bwd_jvp_second(ctx.native_ctx, input, ctx.directions, params, doutput, djv, dsecond)
+        return None, None, None, params_grad, None
+
+
 class Module(torch.nn.Module):
     def __init__(self, seed=1337):
         super().__init__()
@@ -519,8 +567,9 @@ class Module(torch.nn.Module):
             return self._value_and_jvp_differentiable(x, None, layout)
         return self._value_and_jvp(x, None, layout, unit_call=self._grid_in_front())
 
-    def _value_and_jvp_differentiable(self, x, v, layout):
-        """v [B, K, D] or None (the unit vectors): (y, Jv [B, n_output_dims, K]) with a graph to the parameters"""
+    def _value_and_jvp_differentiable(self, x, v, layout, second=False):
+        """v [B, K, D] or None (the unit vectors): (y, Jv [B, n_output_dims, K]) with a graph to the parameters; second:
+        and q [B, n_output_dims]"""
         if layout != "aos":
             raise ValueError(f"differentiable=True serves layout='aos' only (batch-contiguous matrices are not implemented), got {layout!r}")
         if x.requires_grad or (v is not None and v.requires_grad):
@@ -540,6 +589,10 @@ class Module(torch.nn.Module):
             return t.to(torch.float).contiguous()
 
         params = self.params.to(self.native_tcnn_module._param_dtype).contiguous()
+        if second:
+            y, jv, q = _jvp_second_function.apply(self.native_tcnn_module, prepare(x), None if v is None else prepare(v.to(x.device)),
+                                                  params, self.n_output_dims)
+            return y[:batch_size, :self.n_output_dims], jv[:batch_size], q[:batch_size]
         y, jv = _jvp_function.apply(self.native_tcnn_module, prepare(x), None if v is None else prepare(v.to(x.device)), params,
                                     self.n_output_dims)
         return y[:batch_size, :self.n_output_dims], jv[:batch_size]
@@ -601,7 +654,7 @@ class Module(torch.nn.Module):
                 return (y, jac) if batch_size == padded else (y[:, :batch_size], jac[:, :, :batch_size])
             return y[:batch_size, :self.n_output_dims], jac[:batch_size]
 
-    def value_jvp_and_second(self, x, v=None, layout="aos"):
+    def value_jvp_and_second(self, x, v=None, layout="aos", differentiable=False):
         """value_and_jvp and the summed second directional derivatives, in one forward-mode launch that keeps nothing
         (tcnn_module_inference_jvp_second, the "forward Laplacian"):
         layout="aos": x [B, n_input_dims], v [B, K, n_input_dims] -> (y [B, n_output_dims], Jv [B, n_output_dims, K],
@@ -610,7 +663,13 @@ class Module(torch.nn.Module):
                       q [n_output_dims, B]),
         with q[b, o] = sum_k v[b, k]^T (d^2 y_o / dx^2) v[b, k]; y and Jv are value_and_jvp's bits. A v of [B, D] ([D, B])
         is one direction, K = 1: q is the curvature along it and Jv drops the K axis. v=None: the unit vectors, Jv the
-        Jacobian and q the Laplacian. Inference only, as value_and_jacobian; served by the modules it serves."""
+        Jacobian and q the Laplacian. Inference only, as value_and_jacobian; served by the modules it serves.
+        differentiable=True (opt-in; the default is the call above, bit for bit): y, Jv and q carry the same bits and an
+        autograd graph to the parameters, so a loss on the Laplacian (a Poisson residual, a curvature term) trains the
+        module in one keeping forward and one reverse pass (tcnn_module_forward_jvp_second /
+        tcnn_module_backward_jvp_second). layout="aos" only, at most 3 directions (the Laplacian counts as
+        n_input_dims), widths 16, 32 and 64, gradients for the parameters only: x or v requiring grad, layout="soa" and
+        a double backward each raise a ValueError."""
         if layout not in ("aos", "soa"):
             raise ValueError(f"layout must be 'aos' or 'soa', got {layout!r}")
         if v is not None and v.dim() not in (2, 3):
@@ -619,6 +678,9 @@ class Module(torch.nn.Module):
         one = v is not None and v.dim() == 2
         if one:
             v = v.unsqueeze(0 if soa else 1)
+        if differentiable:
+            y, jv, q = self._value_and_jvp_differentiable(x, v, layout, second=True)
+            return y, (jv.squeeze(2) if one else jv), q
         with torch.no_grad():
             if not x.is_cuda:
                 warnings.warn("input must be a CUDA tensor, but isn't. This indicates suboptimal performance.")
@@ -643,10 +705,11 @@ class Module(torch.nn.Module):
                 y, jv, q = y[:batch_size, :self.n_output_dims], jv[:batch_size], q[:batch_size]
             return y, (jv.squeeze(1 if soa else 2) if one else jv), q
 
-    def value_jacobian_and_laplacian(self, x, layout="aos"):
+    def value_jacobian_and_laplacian(self, x, layout="aos", differentiable=False):
         """value_jvp_and_second with the unit vectors: (y, J [B, n_output_dims, n_input_dims], the Laplacian
-        sum_d d^2 y_o / dx_d^2 [B, n_output_dims]); layout="soa": J [n_output_dims, n_input_dims, B], [n_output_dims, B]"""
-        return self.value_jvp_and_second(x, None, layout)
+        sum_d d^2 y_o / dx_d^2 [B, n_output_dims]); layout="soa": J [n_output_dims, n_input_dims, B], [n_output_dims, B].
+        differentiable=True: as value_jvp_and_second."""
+        return self.value_jvp_and_second(x, None, layout, differentiable)
 
     def __getstate__(self):
         """modules.py:194-199: pickle everything except the native module (a C-ABI handle)."""
