@@ -171,6 +171,26 @@ int tcnn_module_inference_jvp(tcnn_module* m, void* stream, uint32_t n, const fl
 int tcnn_module_inference_jvp_second(tcnn_module* m, void* stream, uint32_t n, const float* input, const float* directions,
                                      uint32_t n_directions, void* output, float* jvp, float* second, const void* params,
                                      uint32_t layouts);
+/* tcnn_module_inference_jvp with every second directional derivative in the same launch, the input Hessian (beyond the
+ * reference): output and jvp as tcnn_module_inference_jvp writes them, to the bit, and
+ * hessian[b][o][k][k'] = directions[b][k]^T (d^2 output_o / d input^2) directions[b][k'], fp32
+ * [n][n_output_dims][n_directions][n_directions]. Both triangles are written, with the same bits, and a diagonal entry
+ * carries the bits of tcnn_module_inference_jvp_second's second for that direction alone. directions == NULL means the
+ * n_input_dims unit vectors: n_directions is then 0 or n_input_dims, jvp is the Jacobian and hessian is
+ * d^2 output_o / d input_d d input_d'. Tangent directions give v_i^T H v_j, the shape operator's entries. Nothing is
+ * kept, and no element is accumulated in memory: the result is bit-reproducible.
+ * `layouts` as tcnn_module_inference_jvp_second; under TCNN_LAYOUT_SOA_OUTPUT hessian is
+ * [n_output_dims * n_directions * n_directions][n], row (o * n_directions + k) * n_directions + k'. Each result is the
+ * AoS call's to the bit, transposed. n: a multiple of 128.
+ * Served by the modules tcnn_module_inference_jvp_second serves, with at most 3 directions (NULL directions count as
+ * n_input_dims). Any other module answers "<name>[ behind <encoding>]: inference_hessian is not implemented by the
+ * MI355X engine yet (fp32 FullyFusedMLP network modules alone, behind a lone Identity encoding or behind a lone grid
+ * encoding only)[: <what is not served>]"; width 128 answers it with ": a width of 128 (16, 32 and 64 are served)",
+ * four directions with ": 4 directions (at most 3 are served)", and Sine answers that it has no backward from its
+ * forward value. */
+int tcnn_module_inference_hessian(tcnn_module* m, void* stream, uint32_t n, const float* input, const float* directions,
+                                  uint32_t n_directions, void* output, float* jvp, float* hessian, const void* params,
+                                  uint32_t layouts);
 /* Training through tcnn_module_inference_jvp (beyond the reference): dL/dparams of a loss L(output, jvp) on the value
  * and on the directional derivatives, for all outputs and all directions in one reverse pass.
  * tcnn_module_forward_jvp is tcnn_module_inference_jvp on AoS matrices (layouts 0), the same bits in output and jvp,

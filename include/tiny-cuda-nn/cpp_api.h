@@ -107,6 +107,13 @@ public:
 	                                  uint32_t = 0) {
 		throw std::runtime_error(name() + ": inference_jvp_second is not implemented");
 	}
+	// Beyond the reference: inference_jvp and hessian[b][o][k][k'] = directions[b][k]^T (d^2 output_o / d input^2)
+	// directions[b][k'] in the same launch (tcnn_module_inference_hessian), at most 3 directions; null directions give
+	// the Jacobian and the input Hessian. What inference_jvp_second serves; any other module throws.
+	virtual void inference_hessian(hipStream_t, uint32_t, const float*, const float*, uint32_t, void*, float*, float*, const void*,
+	                               uint32_t = 0) {
+		throw std::runtime_error(name() + ": inference_hessian is not implemented");
+	}
 	// Beyond the reference: inference_jvp keeping a context, and its reverse pass, dL_dparams (fp32, overwritten) of a
 	// loss on the output and on the product (tcnn_module_forward_jvp / tcnn_module_backward_jvp). dL_doutput or dL_djvp
 	// may be null (zero), not both. dL/dinput and dL/ddirections are not produced.
@@ -182,6 +189,10 @@ public:
 	void inference_jvp_second(hipStream_t stream, uint32_t n, const float* input, const float* directions, uint32_t n_directions,
 	                          void* output, float* jvp, float* second, const void* params, uint32_t layouts = 0) override {
 		check(tcnn_module_inference_jvp_second(m_h, stream, n, input, directions, n_directions, output, jvp, second, params, layouts));
+	}
+	void inference_hessian(hipStream_t stream, uint32_t n, const float* input, const float* directions, uint32_t n_directions,
+	                       void* output, float* jvp, float* hessian, const void* params, uint32_t layouts = 0) override {
+		check(tcnn_module_inference_hessian(m_h, stream, n, input, directions, n_directions, output, jvp, hessian, params, layouts));
 	}
 	Context forward_jvp(hipStream_t stream, uint32_t n, const float* input, const float* directions, uint32_t n_directions, void* output,
 	                    float* jvp, const void* params) override {

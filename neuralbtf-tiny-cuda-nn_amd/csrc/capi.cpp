@@ -148,6 +148,16 @@ struct ModuleBase {
 	virtual void inference_jvp_second(hipStream_t, uint32_t, const float*, const float*, uint32_t, void*, float*, float*, const void*, uint32_t) {
 		refuse_jvp_second();
 	}
+	// That launch with every second directional derivative (tcnn_module_inference_hessian): the modules
+	// inference_jvp_second serves, with at most 3 directions
+	void refuse_hessian(const std::string& front = "", const std::string& why = "") const {
+		throw std::runtime_error(name() + (front.empty() ? "" : " behind " + front) +
+		                         ": inference_hessian is not implemented by the MI355X engine yet (fp32 FullyFusedMLP network modules "
+		                         "alone, behind a lone Identity encoding or behind a lone grid encoding only)" + (why.empty() ? "" : ": " + why));
+	}
+	virtual void inference_hessian(hipStream_t, uint32_t, const float*, const float*, uint32_t, void*, float*, float*, const void*, uint32_t) {
+		refuse_hessian();
+	}
 	// Training through value and Jacobian-vector products (tcnn_module_forward_jvp / tcnn_module_backward_jvp): what
 	// inference_jvp serves, on AoS matrices, in batches of 256, with at most 3 directions (1 at width 128)
 	void refuse_jvp_train(const std::string& front = "", const std::string& why = "") const {
@@ -433,6 +443,25 @@ struct ModuleNWIEF32 : ModuleBase {
 		TCNN_CHECK(in && out && jvp && second && params,
 		           "inference_jvp_second needs the input, the output, the product, the second-order sum and the parameters");
 		model.jvp_second(st, n, in, directions, n_directions, (const float*)params, (float*)out, jvp, second, F32Layouts(mask));
+	}
+	// inference_jvp with v_k^T H v_k' per output and pair of directions in the same launch (beyond the reference): the
+	// Hessian d^2 y_o / dx_d dx_d' under null directions. hessian follows the output bit like the product.
+	void inference_hessian(hipStream_t st, uint32_t n, const float* in, const float* directions, uint32_t n_directions, void* out, float* jvp,
+	                       float* hessian, const void* params, uint32_t mask) override {
+		TCNN_CHECK(mask < 4, "inference_hessian: layouts takes TCNN_LAYOUT_SOA_INPUT and TCNN_LAYOUT_SOA_OUTPUT only");
+		if (!model.fused_ok()) refuse_hessian();
+		const EncodingHost::Part* lone = model.enc->lone_part();
+		if (!lone || (lone->kind != COMP_IDENTITY && lone->kind != COMP_GRID)) refuse_hessian(model.enc->name());
+		TCNN_CHECK(!model.has_sine(), name() + ": Sine has no backward from its forward value: inference_hessian serves the other eight "
+		                                       "activations (use inference for the value)");
+		TCNN_CHECK(directions ? n_directions >= 1 : (n_directions == 0 || n_directions == model.n_input_dims),
+		           "inference_hessian: n_directions must be at least 1, or 0 or the input width with null directions (the unit vectors)");
+		const std::string why = model.hessian_refusal(directions ? n_directions : model.n_input_dims);
+		if (!why.empty()) refuse_hessian(lone->kind == COMP_GRID ? model.enc->name() : "", why);
+		TCNN_CHECK(n % 128 == 0, "inference_hessian: batch size must be a multiple of 128");
+		if (!n) return;
+		TCNN_CHECK(in && out && jvp && hessian && params, "inference_hessian needs the input, the output, the product, the Hessian and the parameters");
+		model.hessian(st, n, in, directions, n_directions, (const float*)params, (float*)out, jvp, hessian, F32Layouts(mask));
 	}
 	// The same call keeping a context, and its reverse pass: dL/dparams of a loss on the output and on the product
 	// (beyond the reference). AoS matrices only; null directions are the unit vectors and count as n_input_dims.
@@ -840,6 +869,15 @@ int tcnn_module_inference_jvp_second(tcnn_module* m, void* stream, uint32_t n, c
 		TCNN_CHECK(m && m->m, "inference_jvp_second: null module");
 		// an empty batch still answers for the module: a refusal does not depend on n
 		m->m->inference_jvp_second((hipStream_t)stream, n, in, directions, n_directions, out, jvp, second, params, layouts);
+	});
+}
+
+int tcnn_module_inference_hessian(tcnn_module* m, void* stream, uint32_t n, const float* in, const float* directions, uint32_t n_directions,
+                                  void* out, float* jvp, float* hessian, const void* params, uint32_t layouts) {
+	return guard([&] {
+		TCNN_CHECK(m && m->m, "inference_hessian: null module");
+		// an empty batch still answers for the module: a refusal does not depend on n
+		m->m->inference_hessian((hipStream_t)stream, n, in, directions, n_directions, out, jvp, hessian, params, layouts);
 	});
 }
 

@@ -518,6 +518,17 @@ bool f32_mlp_jvp2_width_ok(uint32_t W);
 void launch_f32_mlp_jvp2(hipStream_t st, uint32_t B, uint32_t D, uint32_t IN, uint32_t W, uint32_t NH, uint32_t OUTP, uint32_t n_out,
                          const float* params, const float* x, const float* directions, uint32_t n_directions, bool x_soa, float* y, float* jvp,
                          float* second, bool y_soa, int act, int out_act, const GridCall* grid, const float* table, float scale, float offset);
+// launch_f32_mlp_jvp with every second directional derivative, the input Hessian (mlp_f32_hessian.hip): y and jvp as
+// above, to the bit, and hessian[b][o][k][k'] = v_k^T (d^2 y_o / dx^2) v_k', [B][n_out][K][K], both triangles with the
+// same bits; y_soa: [n_out K K][B] (row (o K + k) K + k'). Null directions: jvp is the Jacobian and hessian
+// d^2 y_o / dx_d dx_d'. A diagonal entry carries the bits of launch_f32_mlp_jvp2's second for that direction alone.
+// The modules and the argument checks of launch_f32_mlp_jvp2, with K = n_directions <=
+// f32_mlp_hessian_max_directions(W) (3; 0 at a width not served).
+uint32_t f32_mlp_hessian_max_directions(uint32_t W);
+void launch_f32_mlp_hessian(hipStream_t st, uint32_t B, uint32_t D, uint32_t IN, uint32_t W, uint32_t NH, uint32_t OUTP, uint32_t n_out,
+                            const float* params, const float* x, const float* directions, uint32_t n_directions, bool x_soa, float* y, float* jvp,
+                            float* hessian, bool y_soa, int act, int out_act, const GridCall* grid, const float* table, float scale,
+                            float offset);
 // Training through launch_f32_mlp_jvp (mlp_f32_jvp_train.hip): dL/dparams of a loss L(y, Jv). AoS only, B a multiple of 256,
 // K = n_directions <= f32_mlp_jvp_train_max_directions(W) (3 up to W 64, 1 at W 128), so the forward is one pass.
 uint32_t f32_mlp_jvp_train_max_directions(uint32_t W);

@@ -1367,6 +1367,28 @@ void NetworkF32Host::jvp_second(hipStream_t st, uint32_t B, const float* x, cons
 	                    p->grid ? params + mlp.n_params() + p->param_offset : nullptr, p->f0, p->f1);
 }
 
+std::string NetworkF32Host::hessian_refusal(uint32_t K) const {
+	const std::string why = jvp_second_refusal();
+	if (!why.empty()) return why;
+	const uint32_t max_k = f32_mlp_hessian_max_directions(mlp.width);
+	if (K < 1 || K > max_k) return std::to_string(K) + " directions (at most " + std::to_string(max_k) + " are served)";
+	return "";
+}
+
+void NetworkF32Host::hessian(hipStream_t st, uint32_t B, const float* x, const float* directions, uint32_t n_directions, const float* params,
+                             float* y, float* Jv, float* hessian, F32Layouts lay) {
+	TCNN_CHECK(directions || n_directions == 0 || n_directions == n_input_dims,
+	           "fp32 network: null directions are the unit vectors: n_directions must be 0 or the input width");
+	const uint32_t K = directions ? n_directions : n_input_dims;
+	const std::string why = hessian_refusal(K);
+	TCNN_CHECK(why.empty(), "fp32 network: no input Hessian: " + why);
+	const EncodingHost::Part* p = enc->lone_part();
+	const GridCall gc = p->grid ? p->grid->call() : GridCall{};
+	launch_f32_mlp_hessian(st, B, n_input_dims, mlp.n_input, mlp.width, mlp.n_hidden_layers, mlp.padded_output, n_output_dims, params, x,
+	                       directions, K, lay.input, y, Jv, hessian, lay.output, mlp.activation, mlp.output_activation, p->grid ? &gc : nullptr,
+	                       p->grid ? params + mlp.n_params() + p->param_offset : nullptr, p->f0, p->f1);
+}
+
 std::string NetworkF32Host::jvp_train_refusal(uint32_t B, uint32_t K) const {
 	const std::string why = jvp_refusal();
 	if (!why.empty()) return why;

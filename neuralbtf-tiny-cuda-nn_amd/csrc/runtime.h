@@ -568,6 +568,13 @@ struct NetworkF32Host {
 	std::string jvp_second_refusal() const;
 	void jvp_second(hipStream_t st, uint32_t B, const float* x, const float* directions, uint32_t n_directions, const float* params, float* y,
 	                float* Jv, float* second, F32Layouts lay = {});
+	// jvp() with every second directional derivative in the same launch (mlp_f32_hessian.hip): y and Jv carry jvp()'s
+	// bits and hessian[b][o][k][k'] = v_k^T (d^2 y_o / dx^2) v_k', [B][n_output_dims][K][K], both triangles; lay.output:
+	// [n_output_dims K K][B], row (o K + k) K + k'. Null directions give the Jacobian and d^2 y_o / dx_d dx_d'. Served
+	// when hessian_refusal(K) is empty: jvp_second_refusal(), and K <= 3 (the unit vectors count as n_input_dims).
+	std::string hessian_refusal(uint32_t K) const;
+	void hessian(hipStream_t st, uint32_t B, const float* x, const float* directions, uint32_t n_directions, const float* params, float* y,
+	             float* Jv, float* hessian, F32Layouts lay = {});
 	// Training through jvp() (mlp_f32_jvp_train.hip): dL/dparams of a loss L(y, Jv). jvp_forward is jvp() on AoS
 	// matrices, the same bits in y and Jv, and fills keep (jvp_keep_floats(B, K) floats; K counts the unit vectors as
 	// n_input_dims). jvp_backward takes dL_dy [B][padded_output] and dL_dJv [B][n_output_dims][K] (either null: zero, not

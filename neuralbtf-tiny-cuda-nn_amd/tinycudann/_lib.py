@@ -46,6 +46,8 @@ _SIGS = {
     "tcnn_module_inference_jvp": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_uint32]),
     "tcnn_module_inference_jvp_second": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p,
                                                  c_uint32]),
+    "tcnn_module_inference_hessian": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                              c_uint32]),
     "tcnn_module_forward_jvp": (c_void_p, [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p]),
     "tcnn_module_backward_jvp": (c_int, [c_void_p, c_void_p, c_void_p, c_uint32] + [c_void_p] * 6),
     "tcnn_module_forward_jvp_second": (c_void_p, [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p,

@@ -272,6 +272,24 @@ class _NativeModule:
                                                          3 if soa else 0))
         return out, jv, second
 
+    def hessian(self, input, directions, params, n_out, soa):
+        """tcnn_module_inference_hessian: jvp() and hessian [B, n_out, K, K] (soa: [n_out, K, K, B]) =
+        v_k^T (d^2 output / d input^2) v_k' in the same launch"""
+        assert input.dtype == torch.float32 and input.is_contiguous() and input.shape[0 if soa else 1] == self._n_in
+        assert params.dtype == self._param_dtype and params.numel() == self._n_params
+        B, D, dev = input.shape[1 if soa else 0], self._n_in, input.device
+        K = D if directions is None else directions.shape[0 if soa else 1]
+        if directions is not None:
+            assert directions.dtype == torch.float32 and directions.is_contiguous()
+            assert tuple(directions.shape) == ((K, D, B) if soa else (B, K, D))
+        out = torch.empty((n_out, B) if soa else (B, self._n_out), dtype=self._out_dtype, device=dev)
+        jv = torch.empty((n_out, K, B) if soa else (B, n_out, K), dtype=torch.float32, device=dev)
+        hess = torch.empty((n_out, K, K, B) if soa else (B, n_out, K, K), dtype=torch.float32, device=dev)
+        L.check(L.lib().tcnn_module_inference_hessian(self.h, _stream(input), B, _ptr(input), _ptr(directions),
+                                                      0 if directions is None else K, _ptr(out), _ptr(jv), _ptr(hess), _ptr(params),
+                                                      3 if soa else 0))
+        return out, jv, hess
+
     def fwd_jvp(self, input, directions, params, n_out):
         """tcnn_module_forward_jvp: jvp() on AoS matrices, keeping a context for bwd_jvp"""
         B, D = input.shape[0], self._n_in
@@ -710,6 +728,50 @@ class Module(torch.nn.Module):
         sum_d d^2 y_o / dx_d^2 [B, n_output_dims]); layout="soa": J [n_output_dims, n_input_dims, B], [n_output_dims, B].
         differentiable=True: as value_jvp_and_second."""
         return self.value_jvp_and_second(x, None, layout, differentiable)
+
+    def value_jvp_and_hessian(self, x, v=None, layout="aos"):
+        """value_and_jvp and every second directional derivative, in one forward-mode launch that keeps nothing
+        (tcnn_module_inference_hessian):
+        layout="aos": x [B, n_input_dims], v [B, K, n_input_dims] -> (y [B, n_output_dims], Jv [B, n_output_dims, K],
+                      H [B, n_output_dims, K, K]);
+        layout="soa": x [n_input_dims, B], v [K, n_input_dims, B] -> (y [n_output_dims, B], Jv [n_output_dims, K, B],
+                      H [n_output_dims, K, K, B]),
+        with H[b, o, k, l] = v[b, k]^T (d^2 y_o / dx^2) v[b, l], symmetric to the bit; y and Jv are value_and_jvp's bits
+        and H[b, o, k, k] is value_jvp_and_second's q for v[:, k] alone. K <= 3. v=None: the unit vectors, Jv the
+        Jacobian and H the input Hessian d^2 y_o / dx_d dx_e (n_input_dims <= 3). Inference only, as
+        value_and_jacobian: no graph is recorded. Served by the modules value_jvp_and_second serves."""
+        if layout not in ("aos", "soa"):
+            raise ValueError(f"layout must be 'aos' or 'soa', got {layout!r}")
+        if v is not None and v.dim() != 3:
+            raise ValueError(f"v must be [B, K, D] ([K, D, B] for layout='soa'), got {tuple(v.shape)}")
+        soa = layout == "soa"
+        with torch.no_grad():
+            if not x.is_cuda:
+                warnings.warn("input must be a CUDA tensor, but isn't. This indicates suboptimal performance.")
+                x = x.cuda()
+            batch_size = x.shape[1 if soa else 0]
+            if v is not None and v.shape[2 if soa else 0] != batch_size:
+                raise ValueError(f"v has another batch size than x: {tuple(v.shape)}")
+            g = _granularity()
+            padded = (batch_size + g - 1) // g * g
+
+            def prepare(t):
+                if batch_size != padded:
+                    t = torch.nn.functional.pad(t, [0, padded - batch_size] if soa else [0, 0] * (t.dim() - 1) + [0, padded - batch_size])
+                return t.to(torch.float).contiguous()
+
+            params = self.params.detach().to(self.native_tcnn_module._param_dtype).contiguous()
+            y, jv, h = self.native_tcnn_module.hessian(prepare(x), None if v is None else prepare(v.to(x.device)), params,
+                                                       self.n_output_dims, soa)
+            if soa:
+                return y[:, :batch_size], jv[:, :, :batch_size], h[..., :batch_size]
+            return y[:batch_size, :self.n_output_dims], jv[:batch_size], h[:batch_size]
+
+    def value_jacobian_and_hessian(self, x, layout="aos"):
+        """value_jvp_and_hessian with the unit vectors: (y, J [B, n_output_dims, n_input_dims], the input Hessian
+        [B, n_output_dims, n_input_dims, n_input_dims]); layout="soa": J [n_output_dims, n_input_dims, B],
+        [n_output_dims, n_input_dims, n_input_dims, B]."""
+        return self.value_jvp_and_hessian(x, None, layout)
 
     def __getstate__(self):
         """modules.py:194-199: pickle everything except the native module (a C-ABI handle)."""
